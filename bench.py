@@ -56,10 +56,15 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the C3 line and the 1/8-frame probe")
     ap.add_argument("--no-count", action="store_true", help="skip the reference-order counting pass (no roofline block): for PMC runs")
     ap.add_argument("--cpu-spp", type=int, default=16)
-    ap.add_argument("--dump-film", default="", help="rank 0 writes the frame of the last timed step (float32 [pixels, 4], after the reduce) to this .npy file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/film.npy: the frame, float32 [pixels, 4] (xyz + filter weight), after the reduce; "
+                         "a frame over 64 MB is cut to a fixed seeded sample of its pixels, whose indices go to DIR/film_pixels.npy (float64)")
     ap.add_argument("--watchdog", type=int, default=1500, help="seconds after which a rank that is still running dumps its stack and exits 1 (a hung collective "
                                                                "then ends the job with a non-zero code instead of holding the box); 0 = off")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_spawn(args):
@@ -297,6 +302,23 @@ def roofline_block(counts, count_scale, stats, traffic, traffic_note, stale, ms_
                                     "limiters": stale.get("limiters")}
     out["shade"] = sh
     return out
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(d, film):
+    """the last timed step's frame as DIR/film.npy; over DUMP_BYTES_MAX, the same fixed seeded sample of pixels every run (indices in film_pixels.npy)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rows_max = (DUMP_BYTES_MAX - 4096) // (film.itemsize * film.shape[1] + 8)   # (8: a float64 pixel index per sampled row; 4096: the two .npy headers)
+    if film.nbytes > DUMP_BYTES_MAX - 4096:
+        idx = np.sort(np.random.default_rng(20261015).choice(film.shape[0], rows_max, replace=False))
+        film = film[idx]
+        np.save(os.path.join(d, "film_pixels.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(d, "film_pixels.npy")):
+        os.remove(os.path.join(d, "film_pixels.npy"))   # (left by an earlier, larger frame: film.npy is whole now)
+    np.save(os.path.join(d, "film.npy"), np.ascontiguousarray(film, np.float32))
 
 
 def time_steps(step, fence, n):
@@ -579,9 +601,9 @@ def main():
                     lib.render_device(m["ds"], rd8, m["film"].data_ptr())  # warm-up (allocations sized for the shard)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                st8 = [lib.render_device(m["ds"], rd8, m["film"].data_ptr()) for _ in range(2)]
+                st8 = [lib.render_device(m["ds"], rd8, m["film"].data_ptr()) for _ in range(args.steps)]
                 torch.cuda.synchronize()
-                shard_ms.append((time.perf_counter() - t0) / 2 * 1e3)
+                shard_ms.append((time.perf_counter() - t0) / args.steps * 1e3)
             t1 = elapsed / args.steps * 1e3
             extra["eighth_frame_probe"] = {"ms": shard_ms[0], "samples": st8[0]["samples"], "full_frame_ms": t1, "shard_ms": shard_ms,
                                            "predicted_8gpu_speedup_before_reduce": t1 / max(shard_ms),
@@ -590,7 +612,7 @@ def main():
             m["ds"].close()
             del m
             # C3: the north-star configuration (>= 100x CPU on the 4.3 M-triangle scene), timed by the same harness
-            C3_STEPS = 5
+            C3_STEPS = args.steps
             m3 = measure(args, lib, scenes, "statue", C3_STEPS, 1, (0, 1, 64), 1, False, None, fence, count_spp_div=16)
             s3 = float(m3["stats"][0]["samples"])
             c3 = {"metric": "Mpath-samples/sec", "value": s3 * C3_STEPS / m3["elapsed"] / 1e6, "unit": "Msamples/s", "steps": C3_STEPS, "warmup": 1,
@@ -617,9 +639,8 @@ def main():
         if shared_devices:
             out["config"]["note"] = ("%d ranks on %d device(s): a run of the N > 1 CONTROL FLOW (spawn, id exchange, tile deal, film sum, max-over-ranks timing), "
                                      "not a scaling measurement" % (world, n_dev))
-        if args.dump_film:
-            import numpy as np
-            np.save(args.dump_film, m_film_host.numpy().reshape(-1, 4))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m_film_host.numpy().reshape(-1, 4))
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -743,7 +743,7 @@ def test_bench_two_ranks_share_one_device(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     lines = {}
     for n in (1, 2):
-        r = subprocess.run([sys.executable, bench, "--gpus", str(n), "--dump-film", str(tmp_path / ("film%d.npy" % n))] + common, env=env, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, bench, "--gpus", str(n), "--dump-outputs", str(tmp_path / ("out%d" % n))] + common, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         js = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(js) == 1, r.stdout
@@ -751,7 +751,7 @@ def test_bench_two_ranks_share_one_device(tmp_path):
     one, two = lines[1], lines[2]
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["config"]["samples_per_step"] == one["config"]["samples_per_step"] == 96 * 96 * 4
     assert two["scaling"] == "strong" and two["value"] > 0 and two["config"]["librccl"] and "librccl" in two["config"]["librccl"]
-    f1, f2 = np.load(tmp_path / "film1.npy"), np.load(tmp_path / "film2.npy")
+    f1, f2 = np.load(tmp_path / "out1" / "film.npy"), np.load(tmp_path / "out2" / "film.npy")
     assert f1.shape == f2.shape == (96 * 96, 4)
     assert np.array_equal(f1[:, 3], f2[:, 3]) and np.allclose(f1, f2, rtol=1e-6, atol=1e-7)
     assert f1[:, 3].min() > 0
