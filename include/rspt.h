@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 21
+#define RSPT_ABI_VERSION 22
 
 /* error codes */
 #define RSPT_OK 0
@@ -462,7 +462,13 @@ typedef struct {
  * MediumInterface::default().outside, api.rs:1638-1645).  As in v0.9.12: the BSDF- / phase-sampled half of estimate_direct is
  * multiplied by a transmittance that starts at Spectrum::default() = 0 (integrator.rs:531-536, scene.rs:79-106) and so adds nothing;
  * a ray that leaves the scene ends its path even after scattering in a medium (volpath.rs:288-345). */
-enum { RSPT_INTEGRATOR_PATH = 0, RSPT_INTEGRATOR_AO = 1, RSPT_INTEGRATOR_DIRECT = 2, RSPT_INTEGRATOR_VOLPATH = 3 };
+/* RSPT_INTEGRATOR_WHITTED (ABI 22): WhittedIntegrator::li (src/integrators/whitted.rs:43-117) with max_depth (default 5, api.rs:246-252; 0 and 1
+ * both mean no specular recursion).  Every light gets one sampler.get_2d() and one light_sample_li per shading node, in scene order, with one
+ * shadow ray and no BSDF-sampled (MIS) ray; then specular_reflect / specular_transmit as for RSPT_INTEGRATOR_DIRECT, with materials flattened
+ * with allow_multiple_lobes = false.  rr_threshold, light_strategy, direct_strategy, n_light_samples and ao_* are ignored.  Refused like
+ * directlighting (RSPT_E_UNSUPPORTED, the message names whitted): max_depth > 32; moving object instances next to a dynamic material under a
+ * pixel sampler; a camera sample that draws more than the sampler's dimensions (Sobol' 1024, Halton what the permutation table covers). */
+enum { RSPT_INTEGRATOR_PATH = 0, RSPT_INTEGRATOR_AO = 1, RSPT_INTEGRATOR_DIRECT = 2, RSPT_INTEGRATOR_VOLPATH = 3, RSPT_INTEGRATOR_WHITTED = 4 };
 enum { RSPT_DIRECT_SAMPLE_ALL = 0, RSPT_DIRECT_SAMPLE_ONE = 1 };
 
 typedef struct { float o[3], d[3], t_max; uint32_t id; } rspt_ray;   /* 32 B */

@@ -64,8 +64,10 @@ struct DlHit {
 // TEX: the node's texture results are in pb.tex (k_dl_texture ran for it): the material's lobes are bound to them and Material::bump's shading geometry replaces the
 // interpolated one, as in shade_path (kernels.h).  k_dl_hit, which runs before the texture stage, passes false: what it reads of the BSDF — specular lobes — does not exist in
 // the scenes the wavefront form serves with textures (the host routes textures + specular lobes to the per-lane form).
+// n_pre (WhittedIntegrator): receives the shading normal as it was before Material::bump (whitted.rs:58 reads isect.shading.n before
+// compute_scattering_functions); nullptr for directlighting
 template <uint32_t F = SF_ALL, bool TEX = false>
-RDEV void dl_interaction(const SceneDev& sc, const PathBuf& pb, uint32_t slot, uint32_t prim, float4 hc, f3 ray_d, DlHit* o) {
+RDEV void dl_interaction(const SceneDev& sc, const PathBuf& pb, uint32_t slot, uint32_t prim, float4 hc, f3 ray_d, DlHit* o, f3* n_pre = nullptr) {
     TriRec tri = load_tri(sc, prim);
     tri_fill<(F & SF_VERTEX) != 0>(sc, prim, tri, hc.y, hc.z, hc.w, &o->h);
     o->wo = -ray_d;
@@ -79,6 +81,7 @@ RDEV void dl_interaction(const SceneDev& sc, const PathBuf& pb, uint32_t slot, u
             if (!sc.inst_fixed) { o->h.material = 0xffffffffu; o->h.area_light = -1; }
         }
     }
+    if (n_pre) *n_pre = o->h.sh_n;
     if (o->h.material != 0xffffffffu) {
         const rspt_material mat = sc.materials[o->h.material];
         Bsdf& b = o->bsdf;
@@ -188,7 +191,10 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_dl_texture(SceneDev sc, TexTable
 // n_arrays = 2 * max_depth * n_lights with LightStrategy::UniformSampleAll (preprocess, directlighting.rs:54-70), else 0
 // dim_limit: the sampler's dimension count (NUM_SOBOL_DIMENSIONS, or what the Halton permutation table covers); the reference panics when a
 // dimension past it is asked for (sobol.rs:119-124), so a camera sample whose stream ends beyond it is reported (dl.error = 2), not rendered
-RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_dl_assign(Batch bt, DlBuf dl, uint32_t n_lights, uint32_t n_arrays, uint32_t sample_all, uint32_t max_depth, uint32_t dim_limit) {
+// WH: WhittedIntegrator::li's schedule (whitted.rs:74-116) — one get_2d per light at every shading node, no sample arrays (n_arrays = 0), then
+// the same specular_reflect / specular_transmit order as directlighting's
+template <bool WH = false>
+__global__ __launch_bounds__(256) void k_dl_assign(Batch bt, DlBuf dl, uint32_t n_lights, uint32_t n_arrays, uint32_t sample_all, uint32_t max_depth, uint32_t dim_limit) {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s >= bt.n) return;
     uint32_t k = 0;
@@ -202,7 +208,8 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_dl_assign(Batch bt, DlBuf dl, ui
         if (stage == 0u) {
             if (__float_as_uint(dl.le_kind[slot].w) != DL_SHADING) continue;
             dl.kidx[slot] = k; dl.dim[slot] = dim;
-            if (n_lights) {
+            if (WH) dim += 2u * n_lights;
+            else if (n_lights) {
                 if (sample_all) {  // lights whose array pair is used up fall back to get_2d() x 2 (integrator.rs:316-329)
                     const uint32_t pairs = n_arrays / 2u, first = k * n_lights;
                     const uint32_t with_arrays = first >= pairs ? 0u : (pairs - first < n_lights ? pairs - first : n_lights);
@@ -458,6 +465,19 @@ RDEV void dl_dims4(const RenderDev& rd, const DlSob& sb, uint64_t index, uint32_
     *a = dl_dims(rd, index, d); *b = dl_dims(rd, index, d + 2u);
 }
 
+// dimensions d, d + 1 at `index` (the Whitted estimate's one get_2d)
+RDEV f2 dl_dims2(const RenderDev& rd, const DlSob& sb, uint64_t index, uint32_t d) {
+    if (sb.tab && d + 2u <= sb.nd && (index >> sb.bits) == 0) {
+        uint32_t x0 = 0, x1 = 0;
+        for (uint64_t i = index; i != 0; i &= i - 1) {
+            const uint32_t* row = sb.tab + (uint32_t)__builtin_ctzll(i) * sb.nd + d;
+            x0 ^= row[0]; x1 ^= row[1];
+        }
+        return f2{fminf((float)x0 * 0x1.0p-32f, RSPT_ONE_MINUS_EPS), fminf((float)x1 * 0x1.0p-32f, RSPT_ONE_MINUS_EPS)};
+    }
+    return dl_dims(rd, index, d);
+}
+
 // the (u_light, u_scatter, light, choice pdf) of estimate (j, kk) of a node — the sample-value part of k_dl_nee, unchanged
 RDEV bool dl_estimate_samples(const RenderDev& rd, const DlSob& sb, const Batch& bt, const PathBuf& pb, const DlBuf& dl, const uint32_t* __restrict__ pix_list, uint32_t slot, uint32_t nl,
                               uint32_t j, uint32_t kk, uint32_t n_j, uint32_t n_arrays, uint32_t sample_all, f2* u_light, f2* u_scatter, uint32_t* light_num, float* choice_pdf) {
@@ -564,15 +584,52 @@ RDEVN uint32_t dl_estimate(const SceneDev& sc, const DlSob& sb, const PathBuf& p
     return fl | 0x100u;
 }
 
+// WhittedIntegrator::li's term of one light (whitted.rs:74-101) for a built interaction: light_sample_li, and when neither li nor pdf is zero and
+// bsdf.f(wo, wi, BsdfAll) is not black, one shadow ray (virtual slot v, as estimate_direct's) whose term waits in nee_c1.  No BSDF sample, no MIS.
+// The term is the text's ((f * li) * |wi . n|) / pdf — Spectrum * Float, then a per-channel division (spectrum.rs:1752-1762) — with n the shading
+// normal from before the bump map (n_pre).
+template <uint32_t F>
+RDEVN uint32_t wh_estimate(const SceneDev& sc, const DlSob& sb, const PathBuf& pb, const DlHit& d, f3 n_pre, uint32_t light_num, f2 u, uint32_t v, bool* want_sh) {
+    const Hit& h = d.h;
+    uint32_t fl = 0;
+    const rspt_light lt = dl_light(sc, sb, light_num);
+    const bool is_area = !(F & (SF_L_POINT | SF_L_SPOT | SF_L_DISTANT | SF_L_INFINITE)) || lt.kind == RSPT_LIGHT_DIFFUSE_AREA;
+    TriRec lt_tri{};
+    if (is_area) lt_tri = dl_light_tri(sc, sb, lt, light_num);
+    rgb c = mkrgb(0.0f);
+    f3 wi{0.0f, 0.0f, 0.0f};
+    float pdf = 0.0f;
+    LightSample ls;
+    const rgb li = light_sample_li<F>(sc, lt, h.p, u, &wi, &pdf, &ls, is_area ? &lt_tri : nullptr);
+    if (!(is_black(li) || pdf == 0.0f)) {
+        const rgb f = d.bsdf.template f<F>(d.wo, wi, BX_ALL);
+        if (!is_black(f)) {   // visibility.unoccluded(scene): spawn_ray_to (interaction.rs:81-94), as estimate_direct's
+            const f3 origin = offset_ray_origin(h.p, h.p_err, h.n, ls.p - h.p);
+            const f3 target = offset_ray_origin(ls.p, ls.p_err, ls.n, origin - ls.p);
+            store_ray(pb.ray_sh + v, origin, target - origin, 1.0f - RSPT_SHADOW_EPS, v);
+            *want_sh = true;
+            c = f * li * absdot(wi, n_pre) / pdf;
+            fl |= DLF_HAS_C1;
+        }
+    }
+    pb.nee_c1[v] = make_float4(c.r, c.g, c.b, 1.0f);
+    return fl | 0x100u;
+}
+
 // nls: n_light_samples per light on the device (nullptr: one each); R = the number of estimates per node = sum_j n_j (sample_all) or 1
 #define RSPT_DL_NEE_ARGS SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, DlBuf dl, const uint32_t* __restrict__ pix_list, const uint32_t* __restrict__ queue, \
                          const uint32_t* __restrict__ count_in, const int32_t* __restrict__ nls, uint32_t R, uint32_t n_arrays, uint32_t sample_all,            \
                          uint32_t* __restrict__ q_any, uint32_t* cnt_any, uint32_t* __restrict__ q_mis, uint32_t* cnt_mis, uint32_t sob_nd, uint32_t sob_bits
-template <uint32_t F>
+// WH: WhittedIntegrator::li's light loop instead (R = n_lights estimates per node, wh_estimate; the host passes sample_all = 1, n_arrays = 0,
+// nls = nullptr, so that k_dl_nee_resolve_all adds the terms one by one in light order).  The node's emitted radiance moves from le_kind to
+// l_all first: whitted.rs adds every light's term to `l` after isect.le(&wo), where directlighting adds one finished sum; k_dl_gather then adds
+// the zero left behind in le_kind and l_all, in that order.  dim_limit (WH): the sampler's dimension count — a node whose stream runs past it
+// draws nothing (k_dl_assign has reported the camera sample).
+template <uint32_t F, bool WH = false>
 __device__ __forceinline__ void dl_nee_all(const SceneDev& sc, const RenderDev& rd, const Batch& bt, const PathBuf& pb, const DlBuf& dl, const uint32_t* __restrict__ pix_list,
                                            const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_in, const int32_t* __restrict__ nls, uint32_t R,
                                            uint32_t n_arrays, uint32_t sample_all, uint32_t* __restrict__ q_any, uint32_t* cnt_any,
-                                           uint32_t* __restrict__ q_mis, uint32_t* cnt_mis, uint32_t sob_nd, uint32_t sob_bits) {
+                                           uint32_t* __restrict__ q_mis, uint32_t* cnt_mis, uint32_t sob_nd, uint32_t sob_bits, uint32_t dim_limit = 0u) {
     const uint32_t n = *count_in;
     const uint32_t nl = sc.n_lights, n_lights_round = sample_all ? nl : 1u;
     // the Sobol' tables of this render's dimensions in LDS (DlSob; sob_nd = 0: Halton, or they do not fit)
@@ -613,6 +670,7 @@ __device__ __forceinline__ void dl_nee_all(const SceneDev& sc, const RenderDev& 
         uint32_t slot = 0;
         bool shading = false;
         DlHit d;
+        f3 n_pre{0.0f, 0.0f, 0.0f};
         if (i < n) {
             slot = queue[i];
             shading = __float_as_uint(dl.le_kind[slot].w) == DL_SHADING;
@@ -620,7 +678,13 @@ __device__ __forceinline__ void dl_nee_all(const SceneDev& sc, const RenderDev& 
                 const float4 hc = pb.hit_cont[slot];
                 const float4* rp = reinterpret_cast<const float4*>(pb.ray_cont + slot);
                 const float4 r0 = rp[0], r1 = rp[1];
-                dl_interaction<F, true>(sc, pb, slot, __float_as_uint(hc.x), hc, f3{r0.w, r1.x, r1.y}, &d);
+                dl_interaction<F, true>(sc, pb, slot, __float_as_uint(hc.x), hc, f3{r0.w, r1.x, r1.y}, &d, WH ? &n_pre : nullptr);
+                if (WH) {   // l = Spectrum::default(); l += isect.le(&wo)
+                    const float4 lk = dl.le_kind[slot];
+                    const rgb l = mkrgb(0.0f) + rgb{lk.x, lk.y, lk.z};
+                    dl.l_all[slot] = make_float4(l.r, l.g, l.b, 0.0f);
+                    dl.le_kind[slot] = make_float4(0.0f, 0.0f, 0.0f, lk.w);
+                }
             }
         }
         // Queue appends, gathered over up to 32 estimates: one atomicAdd per wave, queue and chunk instead of one per estimate.  With an append after every estimate (dl_push)
@@ -660,7 +724,10 @@ __device__ __forceinline__ void dl_nee_all(const SceneDev& sc, const RenderDev& 
                 const uint32_t v = slot * dl.vs + r * dl.vr;
                 if (i < n) {
                     uint32_t fl = 0;
-                    if (shading) {
+                    if (WH && shading) {   // light j's sampler.get_2d(): dimensions dim + 2 j of the node's stream
+                        const uint32_t dd = dl.dim[slot] + 2u * j;
+                        if (dd + 2u <= dim_limit) fl = wh_estimate<F>(sc, sb, pb, d, n_pre, j, dl_dims2(rd, sb, pb.sobol_index[slot / dl.H], dd), v, &want_sh);
+                    } else if (shading) {
                         f2 u_light, u_scatter;
                         uint32_t light_num;
                         float choice_pdf;
@@ -680,6 +747,11 @@ __device__ __forceinline__ void dl_nee_all(const SceneDev& sc, const RenderDev& 
 
 template <uint32_t F>
 __global__ __launch_bounds__(256) void k_dl_nee_all(RSPT_DL_NEE_ARGS) { dl_nee_all<F>(sc, rd, bt, pb, dl, pix_list, queue, count_in, nls, R, n_arrays, sample_all, q_any, cnt_any, q_mis, cnt_mis, sob_nd, sob_bits); }
+// WhittedIntegrator's estimates (dl_nee_all<F, true>): its own instantiation, so that directlighting's kernels stay as they were
+template <uint32_t F>
+__global__ __launch_bounds__(256) void k_wh_nee_all(RSPT_DL_NEE_ARGS, uint32_t dim_limit) {
+    dl_nee_all<F, true>(sc, rd, bt, pb, dl, pix_list, queue, count_in, nls, R, n_arrays, sample_all, q_any, cnt_any, q_mis, cnt_mis, sob_nd, sob_bits, dim_limit);
+}
 template <uint32_t F, int W>   // the same built for W waves per SIMD (a register budget of 512 / W; the compiler spills what does not fit)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) void k_dl_nee_all_w(RSPT_DL_NEE_ARGS) {
     dl_nee_all<F>(sc, rd, bt, pb, dl, pix_list, queue, count_in, nls, R, n_arrays, sample_all, q_any, cnt_any, q_mis, cnt_mis, sob_nd, sob_bits);

@@ -17,7 +17,10 @@ namespace rspt {
 
 #define RSPT_DL_SERIAL_DEPTH 32
 
-template <bool INST, bool ALPHA, class SMP, bool ANIM = false>
+// WH: WhittedIntegrator::li (src/integrators/whitted.rs:43-117) — the same recursion, specular_reflect / specular_transmit being the same text
+// (whitted.rs:127-253 = directlighting.rs:133-258); only the light term at a shading node differs (whitted(): one get_2d and one light_sample_li
+// per light, no MIS, no sample arrays).  The rest of this struct serves both.
+template <bool INST, bool ALPHA, class SMP, bool ANIM = false, bool WH = false>
 struct DlSerial {
     VolSerial<INST, ALPHA, ANIM> base;      // closest(), surface()
     SMP* px;                          // get_1d / get_2d / get_2d_array / va
@@ -123,6 +126,27 @@ struct DlSerial {
         return l;
     }
 
+    // WhittedIntegrator::li's light loop (whitted.rs:74-101): every light in scene order draws its get_2d whether it contributes or not;
+    // l += ((f * li) * |wi . n|) / pdf, n = the shading normal from before the bump map (whitted.rs:58), added to `l` light by light
+    RDEVN rgb whitted(rgb l, const SerialHit& it, const Bsdf& bsdf, f3 n_pre) {
+        const SceneDev& S = base.sc;
+        for (uint32_t j = 0; j < S.n_lights; j++) {
+            const rspt_light lt = S.lights[j];
+            const f2 u = px->get_2d();
+            f3 wi{0.0f, 0.0f, 0.0f};
+            float pdf = 0.0f;
+            LightSample ls;
+            const rgb li = light_sample_li(S, lt, it.h.p, u, &wi, &pdf, &ls);
+            if (is_black(li) || pdf == 0.0f) continue;
+            const rgb f = bsdf.f(it.wo, wi, BX_ALL);
+            if (is_black(f)) continue;
+            const f3 origin = offset_ray_origin(it.h.p, it.h.p_err, it.h.n, ls.p - it.h.p);   // visibility.unoccluded(scene)
+            const f3 target = offset_ray_origin(ls.p, ls.p_err, ls.n, origin - ls.p);
+            if (!occluded(origin, target - origin, 1.0f - RSPT_SHADOW_EPS)) l = l + f * li * absdot(wi, n_pre) / pdf;
+        }
+        return l;
+    }
+
     struct Frame {   // one activation of `li` that is waiting for a specular child
         rgb l, f;    // radiance so far; the BSDF value of the child in flight
         float s;     // |wi . ns| / pdf of that child
@@ -191,6 +215,7 @@ struct DlSerial {
                 } else {
                     Frame& fr = stack[sp];
                     base.surface(r, ray_d, 0u, &fr.it);
+                    const f3 n_pre = fr.it.h.sh_n;   // (Whitted: isect.shading.n before compute_scattering_functions)
                     if (fr.it.h.material == 0xffffffffu) {   // no BSDF: li(isect.spawn_ray(ray.d), depth) (:87-89)
                         if (++walked > base.max_walk) { base.truncated = true; }
                         else {
@@ -248,7 +273,8 @@ struct DlSerial {
                         b.lobes = dyn_l ? dyn_l : S.bxdfs + mat.first_bxdf;
                         b.n = dyn_l ? (dyn_n < 8u ? dyn_n : 8u) : (mat.n_bxdfs < 8u ? mat.n_bxdfs : 8u);
                         if (fr.it.h.area_light >= 0) l = l + light_l(S.lights[fr.it.h.area_light], fr.it.h.n, fr.it.wo);   // isect.le(&wo)
-                        l = l + direct(fr.it, b);
+                        if (WH) l = whitted(l, fr.it, b, n_pre);
+                        else l = l + direct(fr.it, b);
                         if (sp + 1u < base.rd.max_depth && sp + 1u < RSPT_DL_SERIAL_DEPTH) {
                             fr.l = l;
                             f3 co, cd;

@@ -775,7 +775,19 @@ constexpr int RSPT_DL_RETRY_LANE = -1000;   // batch_direct -> the batch loop: r
 int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, void* film_dev, float* li_host, rspt_stats* stats) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
-    s->select_materials(d->integrator != RSPT_INTEGRATOR_DIRECT);  // allow_multiple_lobes: false in DirectLightingIntegrator::li only (directlighting.rs:86)
+    // WhittedIntegrator::li runs on directlighting's machinery (direct.h / dl_serial.h, their WH forms) as UniformSampleAll with one estimate per light and
+    // no sample arrays; max_depth 0 recurses no more than 1 does (whitted.rs:103: depth + 1 < max_depth)
+    const bool whitted = d->integrator == RSPT_INTEGRATOR_WHITTED;
+    rspt_render_desc wd;
+    if (whitted) {
+        wd = *d;
+        wd.direct_strategy = RSPT_DIRECT_SAMPLE_ALL;
+        wd.n_light_samples = nullptr;
+        if (wd.max_depth == 0) wd.max_depth = 1;
+        d = &wd;
+    }
+    const char* dl_name = whitted ? "whitted" : "directlighting";
+    s->select_materials(d->integrator != RSPT_INTEGRATOR_DIRECT && !whitted);  // allow_multiple_lobes: false in DirectLightingIntegrator::li and WhittedIntegrator::li (directlighting.rs:86, whitted.rs:63)
     const bool halton = d->sampler_kind == RSPT_SAMPLER_HALTON;
     const bool sobol = d->sampler_kind == RSPT_SAMPLER_SOBOL;
     const bool pixel_sampler = d->sampler_kind >= RSPT_SAMPLER_RANDOM && d->sampler_kind <= RSPT_SAMPLER_MAXMINDIST;  // one serial chain per tile: tile_serial.h
@@ -799,9 +811,9 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     if (halton && !d->tables.halton_perms) return fail(RSPT_E_INVALID, "null halton permutation table");
     if (!(d->filter_radius[0] > 0.0f) || !(d->filter_radius[1] > 0.0f)) return fail(RSPT_E_INVALID, "bad filter radius");
     if (d->max_depth > 200) return fail(RSPT_E_UNSUPPORTED, "max_depth > 200");
-    if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO && d->integrator != RSPT_INTEGRATOR_DIRECT && d->integrator != RSPT_INTEGRATOR_VOLPATH)
-        return fail(RSPT_E_UNSUPPORTED, "integrator %u (path, ao, directlighting and volpath only)", d->integrator);
-    const bool direct = d->integrator == RSPT_INTEGRATOR_DIRECT;
+    if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO && d->integrator != RSPT_INTEGRATOR_DIRECT && d->integrator != RSPT_INTEGRATOR_VOLPATH && !whitted)
+        return fail(RSPT_E_UNSUPPORTED, "integrator %u (path, ao, directlighting, volpath and whitted only)", d->integrator);
+    const bool direct = d->integrator == RSPT_INTEGRATOR_DIRECT || whitted;   // (the directlighting forms; `whitted` picks their WH instantiations)
     const bool volpath = d->integrator == RSPT_INTEGRATOR_VOLPATH;
     // moving instances under the pixel samplers and in the per-lane directlighting: round 6 (k_tile_serial modes 5 - 8, k_lane_dl<.., ANIM>); dynamic materials next to them under a
     // pixel sampler are the one combination left without an instantiation
@@ -809,7 +821,8 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
         return fail(RSPT_E_UNSUPPORTED, "a scene with a moving object instance AND a dynamic material (a lobe list that depends on a texture value) under a pixel sampler");
     if (direct) {
         if (d->max_depth < 1 || d->max_depth > (uint32_t)RSPT_DL_SERIAL_DEPTH)
-            return fail(RSPT_E_UNSUPPORTED, "directlighting: max_depth must be in [1, %d] (the explicit recursion stack of the per-lane form, dl_serial.h)", RSPT_DL_SERIAL_DEPTH);
+            return fail(RSPT_E_UNSUPPORTED, "%s: max_depth must be in [%d, %d] (the explicit recursion stack of the per-lane form, dl_serial.h)", dl_name, whitted ? 0 : 1, RSPT_DL_SERIAL_DEPTH);
+        if (whitted && s->dev.n_lights > (1u << 16)) return fail(RSPT_E_UNSUPPORTED, "whitted: more than 65536 lights (one estimate per light and node in one round, direct.h)");
         if (d->direct_strategy > RSPT_DIRECT_SAMPLE_ONE) return fail(RSPT_E_INVALID, "bad direct_strategy");
         for (uint32_t i = 0; s && d->n_light_samples && i < s->dev.n_lights; i++)
             if (d->n_light_samples[i] < 1 || d->n_light_samples[i] > 4096) return fail(RSPT_E_INVALID, "n_light_samples[%u] out of range", i);
@@ -1042,7 +1055,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     // round 6: textured materials WITHOUT specular lobes stay in the wavefront form (every node is a camera hit: k_dl_texture); with specular lobes the children's rays carry
     // reflected / refracted differentials, which only the per-lane form tracks.  RSPT_DL_TEX_WAVEFRONT=0: textures always per lane, as before.  (The estimate kernel of the
     // one-round form is the one that reads the texture results: RSPT_DL_ROUNDS=1 or more than 2^16 estimates per node also send a textured scene to the per-lane form.)
-    bool dl_rounds_one = env_size("RSPT_DL_ROUNDS", 0) == 0;
+    bool dl_rounds_one = whitted || env_size("RSPT_DL_ROUNDS", 0) == 0;   // (whitted's estimates exist in the one-round form only)
     if (dl_rounds_one && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL && s->dev.n_lights) {
         uint64_t r = 0;
         for (uint32_t j = 0; j < s->dev.n_lights; j++) r += d->n_light_samples ? (uint64_t)std::max<int32_t>(d->n_light_samples[j], 0) : 1u;
@@ -1057,7 +1070,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     uint32_t dl_R = 1;
     // (R used to be CLAMPED to 2^20 while the kernels iterate over the unclamped sum — virtual slots would alias.  A sum above 2^16 — hundreds of lights at thousands
     //  of samples each — takes the round-per-estimate form instead, whose slots do not depend on it; n_slots * R then stays far below the RSPT_Q_MIS bit: the batch is <= 2^28 / R)
-    bool dl_one_round = direct && !pixel_sampler && !dl_lane && env_size("RSPT_DL_ROUNDS", 0) == 0;
+    bool dl_one_round = direct && !pixel_sampler && !dl_lane && (whitted || env_size("RSPT_DL_ROUNDS", 0) == 0);
     if (dl_one_round && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL && s->dev.n_lights) {
         uint64_t r = 0;
         for (uint32_t j = 0; j < s->dev.n_lights; j++) r += d->n_light_samples ? (uint64_t)std::max<int32_t>(d->n_light_samples[j], 0) : 1u;
@@ -1302,12 +1315,12 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     auto batch_direct = [&](const Batch& bt, uint32_t& it) -> int {  // DirectLightingIntegrator::li (direct.h): specular tree, dimension assignment, light rounds, gather
         const uint32_t nl = s->dev.n_lights, H = dl_H, md = d->max_depth;
         const bool all = d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL;
-        const uint32_t n_arrays = all ? 2u * md * nl : 0u;
+        const uint32_t n_arrays = (all && !whitted) ? 2u * md * nl : 0u;
         // the sample arrays are filled for every pixel sample whether a node uses them or not (GlobalSampler::start_pixel), so they must fit;
         // the regular stream behind them is checked per camera sample by k_dl_assign against what each tree really draws
         const uint32_t dim_limit = halton ? vol_dim_limit + 1u : 1024u;
         if (5ull + 2ull * n_arrays > dim_limit)
-            return fail(RSPT_E_UNSUPPORTED, "directlighting: %u sample arrays exceed the sampler's %u dimensions", n_arrays, dim_limit);
+            return fail(RSPT_E_UNSUPPORTED, "%s: %u sample arrays exceed the sampler's %u dimensions", dl_name, n_arrays, dim_limit);
         DlBuf dl = g.dl;
         dl.H = H; dl.levels = dl_levels;
         s->dev.time_div = H;   // node h of camera sample s lives in slot s * H + h: its rays carry the sample's time (moving instances); estimate rays: below
@@ -1353,7 +1366,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
                 qcount = &rc_->closest;
             }
         }
-        hipLaunchKernelGGL(k_dl_assign, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, dl, nl, n_arrays, all ? 1u : 0u, md, dim_limit);
+        hipLaunchKernelGGL(whitted ? k_dl_assign<true> : k_dl_assign<false>, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, dl, nl, n_arrays, all ? 1u : 0u, md, dim_limit);
         if (s->has_textures)   // (dl_tex_wave: one level, the roots) the texture stage in front of the estimates
             for (uint32_t l = 0; l < dl_levels; l++)
                 hipLaunchKernelGGL(k_dl_texture, dim3(dgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, g.pb, dl, level_q(l), &g.cnt[l].closest);
@@ -1377,6 +1390,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
                     for (uint64_t v = (uint64_t)std::max<int64_t>(d->spp, 1) * longest; v > 1; v >>= 1) dsb++;
                     dsb = std::min(52u, dsb);
                     dsn = std::min<uint32_t>(1024u, 5u + 2u * n_arrays + 8u * (md + 2u));
+                    if (whitted) dsn = (uint32_t)std::min<uint64_t>(1024u, 5u + (2ull * nl + 4u) * ((1ull << dl_levels) - 1u));   // the deepest tree's stream
                     dsn = std::min<uint32_t>(dsn, (40u * 1024u) / (4u * dsb));
                     if (dsn < 16u) dsn = dsb = 0;
                 }
@@ -1385,6 +1399,10 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
                 const uint32_t dll = (nl <= DL_LDS_LIGHTS && env_size("RSPT_DL_LDS_LIGHTS", 1) != 0) ? nl : 0u;
                 const size_t dl_lds = (dll ? (((size_t)dll * (48 + sizeof(rspt_light)) + 7) / 8) * 8 : 0) + (dsn ? 104 * sizeof(uint64_t) + (size_t)dsn * dsb * sizeof(uint32_t) : 0);
                 dsb |= dll << 16;
+                if (whitted)   // (WhittedIntegrator: one estimate per light, direct.h dl_nee_all<F, true>)
+                    hipLaunchKernelGGL(dl_narrow ? k_wh_nee_all<DLV_PLASTIC> : k_wh_nee_all<SF_ALL>, dim3(dgrid), dim3(256), dl_lds, g.stream, s->dev, rd, bt, g.pb, dl, g.pix_list, level_q(l), &g.cnt[l].closest,
+                                       (const int32_t*)nullptr, dl_R, 0u, 1u, g.q[0][2], &rc_->any, g.q[0][1], &rc_->closest, dsn, dsb, dim_limit);
+                else
                 hipLaunchKernelGGL(dl_narrow ? (dl_waves == 3 ? k_dl_nee_all_w<DLV_PLASTIC, 3> : k_dl_nee_all<DLV_PLASTIC>) : k_dl_nee_all<SF_ALL>, dim3(dgrid), dim3(256), dl_lds, g.stream, s->dev, rd, bt, g.pb, dl, g.pix_list, level_q(l), &g.cnt[l].closest, (const int32_t*)dl_nls, dl_R,
                                    n_arrays, all ? 1u : 0u, g.q[0][2], &rc_->any, g.q[0][1], &rc_->closest, dsn, dsb);
                 ev_close(2, 0);
@@ -1432,35 +1450,41 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
         HIP_TRY(hipMemcpyAsync(&dl_err, dl.error, sizeof dl_err, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
         if (dl_err == 1u) return RSPT_DL_RETRY_LANE;   // a material with several specular lobes of one kind: the lobe choice depends on a sample value, the tree cannot be traced ahead
-        if (dl_err == 3u) return fail(RSPT_E_HIP, "directlighting: a specular bounce in a scene classified as having none");
-        if (dl_err) return fail(RSPT_E_UNSUPPORTED, "directlighting: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dim_limit);
+        if (dl_err == 3u) return fail(RSPT_E_HIP, "%s: a specular bounce in a scene classified as having none", dl_name);
+        if (dl_err) return fail(RSPT_E_UNSUPPORTED, "%s: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dl_name, dim_limit);
         it = md + 4;
         return RSPT_OK;
     };
     auto batch_direct_lane = [&](const Batch& bt, uint32_t& it) -> int {  // the same integrator, one lane per camera sample (lane_serial.h)
         const uint32_t nl = s->dev.n_lights, md = d->max_depth;
         const bool all = d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL;
-        const uint32_t n_arrays = all ? 2u * md * nl : 0u;
+        const uint32_t n_arrays = (all && !whitted) ? 2u * md * nl : 0u;
         const uint32_t dim_limit = halton ? vol_dim_limit + 1u : 1024u;
         if (5ull + 2ull * n_arrays > dim_limit)
-            return fail(RSPT_E_UNSUPPORTED, "directlighting: %u sample arrays exceed the sampler's %u dimensions", n_arrays, dim_limit);
+            return fail(RSPT_E_UNSUPPORTED, "%s: %u sample arrays exceed the sampler's %u dimensions", dl_name, n_arrays, dim_limit);
         HIP_TRY(hipMemsetAsync(dl_words, 0, 2 * sizeof(uint32_t), g.stream));
         const LaneDesc ln{all ? dl_nls : nullptr, n_arrays, all ? 1u : 0u, dim_limit, dl_tex, (uint32_t)dl_lanes, dl_tex_rows, dl_dyn,
                           s->has_null_material ? (uint32_t)env_size("RSPT_NULL_PASSES", 1024) : 0u, dl_words, dl_words + 1};
         const dim3 lgrid((bt.n + 63u) / 64u);
         ev_open(2, 0);
 #define RSPT_LN(I, A) hipLaunchKernelGGL((k_lane_dl<I, A>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln)
-        if (s->has_animated) {   // (round 6: the walk interpolates the instances it enters at the sample's ray time, pb.time)
+#define RSPT_LNW(I, A, M) hipLaunchKernelGGL((k_lane_dl<I, A, M, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln)
+        if (whitted) {   // WhittedIntegrator::li (lane_serial.h k_lane_dl<.., WH>)
+            if (s->has_animated) { if (s->has_alpha) RSPT_LNW(true, true, true); else RSPT_LNW(true, false, true); }
+            else if (s->has_instances) { if (s->has_alpha) RSPT_LNW(true, true, false); else RSPT_LNW(true, false, false); }
+            else { if (s->has_alpha) RSPT_LNW(false, true, false); else RSPT_LNW(false, false, false); }
+        } else if (s->has_animated) {   // (round 6: the walk interpolates the instances it enters at the sample's ray time, pb.time)
             if (s->has_alpha) hipLaunchKernelGGL((k_lane_dl<true, true, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln);
             else hipLaunchKernelGGL((k_lane_dl<true, false, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln);
         } else if (s->has_instances) { if (s->has_alpha) RSPT_LN(true, true); else RSPT_LN(true, false); }
         else { if (s->has_alpha) RSPT_LN(false, true); else RSPT_LN(false, false); }
+#undef RSPT_LNW
 #undef RSPT_LN
         ev_close(2, 0);
         uint32_t w[2] = {0, 0};
         HIP_TRY(hipMemcpyAsync(w, dl_words, sizeof w, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (w[0]) return fail(RSPT_E_UNSUPPORTED, "directlighting: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dim_limit);
+        if (w[0]) return fail(RSPT_E_UNSUPPORTED, "%s: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dl_name, dim_limit);
         truncated += w[1];
         it = 1;
         return RSPT_OK;
@@ -1612,7 +1636,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
         float2* arr = nullptr; uint32_t* arr_sz_d = nullptr; uint32_t* arr_base_d = nullptr; int32_t* nls_d = nullptr;
         std::vector<uint32_t> arr_sz;
         if (ao) arr_sz.push_back(d->ao_n_samples);
-        if (direct && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL)
+        if (direct && !whitted && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL)   // (whitted.rs requests no arrays)
             for (uint32_t lvl = 0; lvl < d->max_depth; lvl++)
                 for (uint32_t j = 0; j < s->dev.n_lights; j++) { const uint32_t n = d->n_light_samples ? (uint32_t)d->n_light_samples[j] : 1u; arr_sz.push_back(n); arr_sz.push_back(n); }
         std::vector<uint32_t> arr_base(arr_sz.size());
@@ -1680,6 +1704,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
             if (s->has_animated) {   // (round 6: modes 5 - 8 = path / ao / volpath / directlighting with the instances' Transforms interpolated at the camera sample's time)
                 if (ao) { if (s->has_alpha) RSPT_TS(true, true, 6); else RSPT_TS(true, false, 6); }
                 else if (volpath) { if (s->has_alpha) RSPT_TS(true, true, 7); else RSPT_TS(true, false, 7); }
+                else if (whitted) { if (s->has_alpha) RSPT_TS(true, true, 10); else RSPT_TS(true, false, 10); }
                 else if (direct) { if (s->has_alpha) RSPT_TS(true, true, 8); else RSPT_TS(true, false, 8); }
                 else { if (s->has_alpha) RSPT_TS(true, true, 5); else RSPT_TS(true, false, 5); }
             } else if (ao) {
@@ -1688,6 +1713,9 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
             } else if (volpath) {
                 if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 2); else RSPT_TS(true, false, 2); }
                 else { if (s->has_alpha) RSPT_TS(false, true, 2); else RSPT_TS(false, false, 2); }
+            } else if (whitted) {   // (modes 9 / 10: WhittedIntegrator::li, tile_serial.h)
+                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 9); else RSPT_TS(true, false, 9); }
+                else { if (s->has_alpha) RSPT_TS(false, true, 9); else RSPT_TS(false, false, 9); }
             } else if (direct) {
                 if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 3); else RSPT_TS(true, false, 3); }
                 else { if (s->has_alpha) RSPT_TS(false, true, 3); else RSPT_TS(false, false, 3); }

@@ -43,6 +43,7 @@ struct PixDesc {              // the sampler's parameters and this render's vect
 // 4: PathIntegrator::li over a scene with dynamic materials (shade_path<.., SF_ALL>: lobe lists built per hit, material_assembly.h).
 // 5 / 6 / 7 / 8 (round 6): modes 0 / 1 / 2 / 3 over a scene with MOVING object instances (AnimatedTransform primitive_to_world, primitive.rs:198-272): the camera sample's time
 // (sampler.rs:88, lerp over the shutter) rides in pb.time[slot] — where shade_path / texture_path read it — and every traversal interpolates the instances it enters.
+// 9 / 10: WhittedIntegrator::li (dl_serial.h DlSerial<.., WH>), without / with moving instances.
 #ifdef RSPT_TS_WAVES   // A/B: the per-tile kernels built for that many waves per SIMD (what does not fit the budget is spilled)
 #define RSPT_TS_ATTR __attribute__((amdgpu_waves_per_eu(RSPT_TS_WAVES, RSPT_TS_WAVES)))
 #else
@@ -64,8 +65,9 @@ __global__ __launch_bounds__(64) RSPT_TS_ATTR void k_tile_serial(SceneDev sc, Te
     px.arr = pd.arr ? pd.arr + t : nullptr; px.arr_sz = pd.arr_sz; px.arr_base = pd.arr_base; px.n_arr = pd.n_arr; px.arr_cur = 0;
     if (row0 == 0) px.rng.set_sequence((uint64_t)tr.seed);  // tile_sampler.reseed(seed) (integrator.rs:114)
     else { px.rng.state = pd.rng_state[2 * (size_t)t]; px.rng.inc = pd.rng_state[2 * (size_t)t + 1]; }
-    constexpr bool ANIM = MODE >= 5 && MODE <= 8;
-    constexpr int M = MODE == 5 ? 0 : (MODE == 6 ? 1 : (MODE == 7 ? 2 : (MODE == 8 ? 3 : MODE)));
+    constexpr bool ANIM = (MODE >= 5 && MODE <= 8) || MODE == 10;
+    constexpr bool WH = MODE == 9 || MODE == 10;
+    constexpr int M = MODE == 5 ? 0 : (MODE == 6 ? 1 : (MODE == 7 ? 2 : (MODE == 8 || WH ? 3 : MODE)));
     static_assert(!ANIM || INST, "moving instances are instances");
     const uint32_t slot = t;   // the lane's own path slot
     uint32_t k = tr.pix0;
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(64) RSPT_TS_ATTR void k_tile_serial(SceneDev sc, Te
                 const float ray_time = ANIM ? rd.shutter_open * (1.0f - time_s) + rd.shutter_close * time_s : 0.0f;   // lerp(sample.time, shutter_open, shutter_close) (perspective.rs:226)
                 if (ANIM) pb.time[slot] = ray_time;
                 if (M == 3) {
-                    DlSerial<INST, ALPHA, PixSampler, ANIM> dl{VolSerial<INST, ALPHA, ANIM>{sc, tt, ld, rd, pb, slot, SerialSampler{&px}, lds, max_iters, false, ray_time}, &px, pd.n_light_samples, pd.direct_strategy == RSPT_DIRECT_SAMPLE_ALL,
+                    DlSerial<INST, ALPHA, PixSampler, ANIM, WH> dl{VolSerial<INST, ALPHA, ANIM>{sc, tt, ld, rd, pb, slot, SerialSampler{&px}, lds, max_iters, false, ray_time}, &px, pd.n_light_samples, pd.direct_strategy == RSPT_DIRECT_SAMPLE_ALL,
                                                          pd.dl_tex ? pd.dl_tex + t : nullptr, n_tiles, pd.dl_tex_rows, p_film, p_lens,
                                                          pd.dl_dyn ? pd.dl_dyn + t : nullptr, n_tiles};
                     const rgb l = dl.li(o, d, t_max);

@@ -98,6 +98,15 @@ RSPT_TU_TS2(true, 7)   /* volpath / directlighting per tile over moving instance
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_TS8)
 RSPT_TU_TS2(true, 8)
 #endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_TS9A)
+RSPT_TU_TS2(false, 9)   /* whitted per tile */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_TS9B)
+RSPT_TU_TS2(true, 9)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_TS10)
+RSPT_TU_TS2(true, 10)   /* whitted per tile over moving instances */
+#endif
 #define RSPT_TU_LANE(I, A) RSPT_TU_X template __global__ void k_lane_dl<I, A>(SceneDev, TexTables, LightDistDev, RenderDev, Batch, PathBuf, const uint32_t*, LaneDesc);
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_LANE_A)
 RSPT_TU_LANE(false, false) RSPT_TU_LANE(false, true)
@@ -108,6 +117,16 @@ RSPT_TU_LANE(true, false) RSPT_TU_LANE(true, true)
 #define RSPT_TU_LANE_ANIM(A) RSPT_TU_X template __global__ void k_lane_dl<true, A, true>(SceneDev, TexTables, LightDistDev, RenderDev, Batch, PathBuf, const uint32_t*, LaneDesc);
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_LANE_C)
 RSPT_TU_LANE_ANIM(false) RSPT_TU_LANE_ANIM(true)   /* the per-lane directlighting over moving instances */
+#endif
+#define RSPT_TU_LANE_WH(I, A, M) RSPT_TU_X template __global__ void k_lane_dl<I, A, M, true>(SceneDev, TexTables, LightDistDev, RenderDev, Batch, PathBuf, const uint32_t*, LaneDesc);
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_LANE_WA)
+RSPT_TU_LANE_WH(false, false, false) RSPT_TU_LANE_WH(false, true, false)   /* whitted, one lane per camera sample */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_LANE_WB)
+RSPT_TU_LANE_WH(true, false, false) RSPT_TU_LANE_WH(true, true, false)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_LANE_WC)
+RSPT_TU_LANE_WH(true, false, true) RSPT_TU_LANE_WH(true, true, true)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_A)
 RSPT_TU_SHADE(SV_DIFFUSE) RSPT_TU_SHADE_W(SV_DIFFUSE, 3) RSPT_TU_SHADE_W(SV_DIFFUSE, 4)

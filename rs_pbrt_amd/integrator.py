@@ -116,6 +116,20 @@ class DirectLightingIntegrator(PathIntegrator):
         return rd
 
 
+class WhittedIntegrator(PathIntegrator):
+    """WhittedIntegrator::new(max_depth, camera, sampler, pixel_bounds) (src/integrators/whitted.rs:28-42), created by the "whitted"
+    integrator name with maxdepth 5 (api.rs:246-252).  One light sample per light at every hit, no MIS, specular reflection and
+    transmission recursed depth first; materials flattened with allow_multiple_lobes = false as for DirectLightingIntegrator."""
+
+    def __init__(self, max_depth=5, camera=None, sampler=None, pixel_bounds=None):
+        super().__init__(max_depth=max_depth, camera=camera, sampler=sampler, pixel_bounds=pixel_bounds)
+
+    def _desc(self, shard=None):
+        rd = super()._desc(shard)
+        rd.integrator = abi.INTEGRATOR_WHITTED
+        return rd
+
+
 class VolPathIntegrator(PathIntegrator):
     """VolPathIntegrator::new(max_depth, camera, sampler, pixel_bounds, rr_threshold, light_sample_strategy) (src/integrators/volpath.rs:38-55),
     created by the "volpath" integrator name with the path integrator's defaults (api.rs:350-380).  Media come with the scene

@@ -965,8 +965,10 @@ def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.
     rd = abi.RenderDesc()
     rd.allow_slow_paths = int(bool(allow_slow_paths))
     # Integrator "path" (path.rs), "ao" / "ambientocclusion" (api.rs:411; ao.rs: nsamples 64, cossample true) or
-    # "directlighting" (api.rs:322-349: strategy "all" | "one", maxdepth 5; light_samples = Light::get_n_samples per light)
-    rd.integrator = {"ao": abi.INTEGRATOR_AO, "directlighting": abi.INTEGRATOR_DIRECT, "volpath": abi.INTEGRATOR_VOLPATH}.get(integrator, abi.INTEGRATOR_PATH)
+    # "directlighting" (api.rs:322-349: strategy "all" | "one", maxdepth 5; light_samples = Light::get_n_samples per light) or "whitted"
+    # (api.rs:246-252: maxdepth 5; strategy and light_samples are ignored there, except that len(light_samples) sizes the Halton table below)
+    rd.integrator = {"ao": abi.INTEGRATOR_AO, "directlighting": abi.INTEGRATOR_DIRECT, "volpath": abi.INTEGRATOR_VOLPATH,
+                     "whitted": abi.INTEGRATOR_WHITTED}.get(integrator, abi.INTEGRATOR_PATH)
     rd.direct_strategy = {"all": abi.DIRECT_SAMPLE_ALL, "one": abi.DIRECT_SAMPLE_ONE}[direct_strategy]
     if light_samples is not None:
         rd._light_samples = np.ascontiguousarray(light_samples, np.int32)  # kept alive by the desc object
@@ -1046,6 +1048,9 @@ def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.
     if integrator == "directlighting":  # sample arrays + a full specular tree on the fall-back stream (rs_pbrt_amd/csrc/direct.h)
         nl = len(light_samples) if light_samples is not None else 16
         n_halton_dims = min(999, 5 + 4 * max_depth * nl + ((1 << max_depth) - 1) * (4 * nl + 4) + 4)
+    if integrator == "whitted":  # a full specular tree: one get_2d per light and two sample_f draws per shading node (whitted.rs:74-116); depth 0 = depth 1
+        nl = len(light_samples) if light_samples is not None else 16
+        n_halton_dims = min(999, 5 + ((1 << max(max_depth, 1)) - 1) * (2 * nl + 4))
     rd.tables = sobol_tables().as_struct(halton_permutations(n_halton_dims) if sampler == "halton" else None)
     return rd
 

@@ -324,7 +324,7 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
             (depth, 1.0, "uniform".to_string(), 2u32, 0u32, 0u32)
         }
         SamplerIntegrator::VolPath(v) => (v.max_depth, v.rr_threshold, v.light_sample_strategy.clone(), 3u32, 0u32, 0u32),   // pub fields (volpath.rs:25-35)
-        _ => return Err("integrator without a GPU path (whitted)".into()),
+        SamplerIntegrator::Whitted(w) => (w.max_depth(), 1.0, "uniform".to_string(), 4u32, 0u32, 0u32),   // RSPT_INTEGRATOR_WHITTED; getter: rs_pbrt.patch (whitted.rs:25)
     };
     let bvh = match &*scene.aggregate { Primitive::BVH(b) => b, _ => return Err("aggregate is not a BVH".into()) };
     let mut f = Flat::default();
