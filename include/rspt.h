@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 22
+#define RSPT_ABI_VERSION 23
 
 /* error codes */
 #define RSPT_OK 0
@@ -55,9 +55,11 @@ typedef struct {
  * each is a GeometricPrimitive wrapping a Triangle (src/core/primitive.rs:100-105,
  * src/shapes/triangle.rs:84-96).  v[] index the global vertex arrays below. */
 #define RSPT_MESH_INSTANCE 0xffffffffu /* rspt_prim.mesh of a TransformedPrimitive: v[0] = index into instances[] */
+#define RSPT_MESH_SPHERE 0xfffffffeu   /* rspt_prim.mesh of a GeometricPrimitive wrapping a Sphere (ABI 23): v[0] = index into spheres[],
+                                          v[1] = v[2] = 0; material and area_light as for a triangle */
 typedef struct {
     uint32_t v[3];
-    uint32_t mesh;       /* index into meshes[], or RSPT_MESH_INSTANCE               */
+    uint32_t mesh;       /* index into meshes[], RSPT_MESH_INSTANCE or RSPT_MESH_SPHERE */
     uint32_t material;   /* index into materials[]; 0xffffffff = no material
                             (path.rs:109-116 passes straight through)               */
     int32_t area_light;  /* index into lights[] or -1 (primitive.rs:193-195)         */
@@ -79,6 +81,23 @@ typedef struct {
      * when the two differ (medium.rs:340-362), otherwise rays keep the medium they travel in (primitive.rs:160-170). */
     uint32_t medium_inside, medium_outside;
 } rspt_mesh; /* 32 B */
+
+/* ---- analytic spheres (ABI 23): what Sphere holds (src/shapes/sphere.rs:21-35), one record per Shape "sphere" ----
+ * object_to_world / world_to_object are the two Transform.m rs_pbrt hands Sphere::new (api.rs), row major, not recomputed; radius, z_min,
+ * z_max, theta_min, theta_max and phi_max (radians) as Sphere::new (sphere.rs:59-84) left them (the clamps and acos already applied).
+ * The library intersects them exactly as Sphere::intersect / intersect_p (sphere.rs:103-360): transform_ray_with_error, the EFloat
+ * quadratic with its f64 discriminant, the bound tests against t_max and 0, the z / phi clipping with the retry on t1.  A hit's t is
+ * t_shape_hit.v.  Served today: rspt_trace / rspt_trace_device and RSPT_LIBM_SPHERE.  rspt_render answers RSPT_E_UNSUPPORTED ("sphere")
+ * for a scene with spheres (the shading, texture and area-light stages are not built for them yet): the caller keeps its CPU loop.
+ * rspt_light_distribution answers the same.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED, "sphere"): spheres together with object
+ * instances.  A DIFFUSE_AREA rspt_light may name a sphere primitive (rendering it is the follow-up). */
+typedef struct {
+    float object_to_world[16];
+    float world_to_object[16];
+    float radius, z_min, z_max, theta_min, theta_max, phi_max;
+    uint32_t reverse_orientation, transform_swaps_handedness;
+    uint32_t medium_inside, medium_outside; /* as in rspt_mesh: 0 = no medium, else 1 + index into media[] */
+} rspt_sphere; /* 168 B */
 
 /* ---- participating media (src/core/medium.rs, src/media/{homogeneous,grid}.rs; MakeNamedMedium api.rs:953-1037) ----
  * sigma_a / sigma_s already multiplied by "scale".  The phase function is HenyeyGreenstein { g } (medium.rs:296-331).
@@ -352,6 +371,9 @@ typedef struct {
     uint32_t instancing_mode;          /* RSPT_INSTANCING_* */
     uint32_t n_media;
     const rspt_medium* media;          /* RenderOptions.named_media, referenced by rspt_mesh.medium_inside / _outside */
+    const rspt_sphere* spheres;        /* ABI 23: the spheres that rspt_prim records with mesh == RSPT_MESH_SPHERE name */
+    uint32_t n_spheres;
+    uint32_t pad_spheres;
 } rspt_scene_desc;
 
 /* Sampler tables owned by the host.
@@ -472,7 +494,8 @@ enum { RSPT_INTEGRATOR_PATH = 0, RSPT_INTEGRATOR_AO = 1, RSPT_INTEGRATOR_DIRECT 
 enum { RSPT_DIRECT_SAMPLE_ALL = 0, RSPT_DIRECT_SAMPLE_ONE = 1 };
 
 typedef struct { float o[3], d[3], t_max; uint32_t id; } rspt_ray;   /* 32 B */
-typedef struct { uint32_t prim; float t, b0, b1, b2; } rspt_hit;     /* prim = 0xffffffff on miss */
+typedef struct { uint32_t prim; float t, b0, b1, b2; } rspt_hit;     /* prim = 0xffffffff on miss; a sphere hit (ABI 23): b0 = b1 = b2 = 0
+                                                                        (prim and t are the contract; RSPT_LIBM_SPHERE gives the rest) */
 
 typedef struct {
     double t_render_s;      /* first launch -> film in host memory                    */
@@ -619,8 +642,13 @@ int rspt_motion_bounds(const float start_m[16], float start_time, const float en
  *                                over Triangle::sample / sample_with_ref_point (lights/diffuse.rs:64-84, triangle.rs:676-744) on a triangle without vertex normals
  *   RSPT_LIBM_LOBE (48 floats per element, in and out)  x = the 29 words of one rspt_bxdf, wo, wi, u[2] -> out = f(wo, wi) pdf(wo, wi) | sample_f(wo, u): value wi pdf sampled_type | get_type:
  *                                one lobe of reflection.rs:711-1478 as the shade kernels evaluate it (the sampled value of a NON-specular lobe is what lobe_f gives: Bsdf::sample_f re-sums it) */
+/* RSPT_LIBM_SPHERE (ABI 23, 64 floats per element, in and out): x = the 42 words of one rspt_sphere, o[3], d[3], t_max -> out[0] = Sphere::intersect's
+ *   result (1 / 0), out[1] = t, then p[3], p_error[3], n[3], uv[2], dpdu[3], dpdv[3], dndu[3], dndv[3] (out[2..24]) and the shading frame n, dpdu, dpdv,
+ *   dndu, dndv (out[25..39]) after object_to_world.transform_surface_interaction (transform.rs:815-860), out[43] = Sphere::intersect_p (1 / 0): the
+ *   functions the traversal kernels call (rs_pbrt_amd/csrc/dev_sphere.h).  Unused outputs are 0.  Codes above 15 answer RSPT_E_INVALID. */
 enum { RSPT_LIBM_SIN = 0, RSPT_LIBM_COS = 1, RSPT_LIBM_LOG = 2, RSPT_LIBM_LOG2 = 3, RSPT_LIBM_EXP = 4, RSPT_LIBM_ACOS = 5, RSPT_LIBM_ATAN2 = 6, RSPT_LIBM_MAT4_INVERSE = 7,
-       RSPT_LIBM_TRIANGLE = 8, RSPT_LIBM_BOX = 9, RSPT_LIBM_OFFSET_RAY_ORIGIN = 10, RSPT_LIBM_MICROFACET = 11, RSPT_LIBM_VECTORS = 12, RSPT_LIBM_AREA_LIGHT = 13, RSPT_LIBM_LOBE = 14 };
+       RSPT_LIBM_TRIANGLE = 8, RSPT_LIBM_BOX = 9, RSPT_LIBM_OFFSET_RAY_ORIGIN = 10, RSPT_LIBM_MICROFACET = 11, RSPT_LIBM_VECTORS = 12, RSPT_LIBM_AREA_LIGHT = 13, RSPT_LIBM_LOBE = 14,
+       RSPT_LIBM_SPHERE = 15 };
 int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* out);
 
 /* Benchmark hook: same as rspt_trace on rays already resident in device memory,

@@ -11,6 +11,7 @@ namespace rspt {
 enum : uint32_t { MF_HAS_N = 1, MF_HAS_S = 2, MF_HAS_UV = 4, MF_FLIP = 8,
                   MF_ALPHA = 16,          // the mesh has an alpha_mask or a shadow_alpha_mask (triangle.rs:39-40)
                   MF_INSTANCE = 0x100,
+                  MF_SPHERE = 0x200,      // ABI 23: the record stands for a Sphere: t0.x = sphere index (dev_sphere.h)
                   MF_MASK_SHIFT = 12 };   // bits 12 .. 31: the mesh's entry in SceneDev::alpha_masks (scenes whose masks all have the simple form)  // the record stands for a TransformedPrimitive: t0.x = instance index, t0.y = the four-box kernel's
                                           // reference to the primitives that follow it in its leaf (RSPT_NONE: it is the last one)
 

@@ -1628,6 +1628,12 @@ RSPT_PLAIN_KERNEL void k_build_tris(const rspt_prim* __restrict__ prims, const r
         tris[3 * (size_t)i + 2] = make_float4(0.0f, __uint_as_float(0xffffffffu), __uint_as_float(0xffffffffu), __uint_as_float((uint32_t)MF_INSTANCE));
         return;
     }
+    if (pr.mesh == RSPT_MESH_SPHERE) {   // ABI 23: a Sphere (dev_sphere.h): sphere index, material, area light, MF_SPHERE; its record follows the primitive records
+        tris[3 * (size_t)i] = make_float4(__uint_as_float(pr.v[0]), 0.0f, 0.0f, 0.0f);
+        tris[3 * (size_t)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        tris[3 * (size_t)i + 2] = make_float4(0.0f, __uint_as_float(pr.material), __uint_as_float((uint32_t)pr.area_light), __uint_as_float((uint32_t)MF_SPHERE));
+        return;
+    }
     rspt_mesh m = meshes[pr.mesh];
     f3 p0 = ld3(P, pr.v[0]), p1 = ld3(P, pr.v[1]), p2 = ld3(P, pr.v[2]);
     uint32_t flags = (m.has_n ? MF_HAS_N : 0u) | (m.has_s ? MF_HAS_S : 0u) | (m.has_uv ? MF_HAS_UV : 0u) | (m.flip ? MF_FLIP : 0u) |

@@ -261,6 +261,7 @@ struct rspt_scene_s {
     std::vector<uint64_t> image_base; // per image: its first float in the texel pool
     bool has_instances = false;       // object instances: two-level traversal (kernels.h traverse<ANY, true>)
     bool has_animated = false;        // ... some of them moving (dev_scene.h inst_at): the reference-order kernel serves the scene, `path` under Sobol' / Halton only
+    bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); served by the trace hook, refused by rspt_render
     std::map<int, LightDist> light_dists;  // by effective strategy
 };
 
@@ -708,6 +709,25 @@ void launch_trace_v(int lane, bool count, uint32_t grid, const rspt_scene_s* s, 
     if (trace_can_overflow(s))
         hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, n_overflow, ovf, ra, rb, oa, ob, occ, hits, hi);
 }
+// Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> on the main stream with every spill row (a non-instanced four-box walk cannot then
+// overflow, so no k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q
+// walks triangle leaves only), no big-workgroup shapes: RSPT_COUNTERS, RSPT_TRACE_KERNEL, RSPT_ANY_Q, RSPT_W4_SHAPE and RSPT_W4_SPILL_ROWS do not
+// apply.  rspt_trace_device checks w4_ok first.
+template <bool ANY>
+void launch_trace_sph(const rspt_scene_s* s, uint32_t n, uint32_t* cursor, const rspt_ray* rays, rspt_hit* hits, uint32_t* xcur) {
+    const SceneDev& sc = s->dev;
+    const uint32_t pgrid = hinted_grid(pw_grid(), RSPT_PW_BLOCK);
+    const int pw_refill = (int)env_size("RSPT_PW_REFILL", RSPT_PW_REFILL), pw_leaf = (int)env_size("RSPT_PW_LEAF", RSPT_PW_LEAF);
+    const uint32_t pw_chunk = (uint32_t)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_CHUNK", RSPT_PW_CHUNK) & ~(size_t)63, 64), 1u << 20);
+    uint32_t* n_overflow = cursor + 2;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, g.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, nullptr, nullptr, n, cursor,
+                           rays, rays, nullptr, nullptr, nullptr, hits, n_overflow, g.ovf, g.spill, (uint32_t)RSPT_W4_SPILL, pw_refill, pw_leaf, s->w4_top, nullptr, xcur, pw_chunk);
+    };
+    if (!s->has_alpha) go(k_trace_w4<ANY, 1, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else if (s->alpha_simple) go(k_trace_w4<ANY, 1, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else go(k_trace_w4<ANY, 1, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+}
 template <bool ANY, int OUT_MODE>
 void launch_trace(int lane, bool count, uint32_t grid, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
                   const rspt_ray* ra, const rspt_ray* rb, float4* oa, float4* ob, uint32_t* occ, rspt_hit* hits, unsigned long long* counters, uint32_t* xcd_cursors = nullptr) {
@@ -715,6 +735,10 @@ void launch_trace(int lane, bool count, uint32_t grid, const rspt_scene_s* s, co
     // OFF by default: measured neutral to slightly negative (C2 474.0 -> 471.5 Msamples/s, C3 stand-in 2015.6 -> 2014.7; L2 hit rate of the closest-hit
     // launches 0.624 -> 0.620 by TCC_HIT / TCC_MISS — profiles/r05_xcd_affine_ab.txt): the tree's L2 hits are its root side, which every XCD holds anyway
     uint32_t* xcur = (xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? xcd_cursors : nullptr;
+    if (s->has_spheres) {   // ABI 23: the sphere instantiations (trace_w4.h SPH) — the hook's output mode only (rspt_render refuses sphere scenes before any launch)
+        if constexpr (OUT_MODE == 1) launch_trace_sph<ANY>(s, count_imm, cursor, ra, hits, xcur);
+        return;
+    }
 #define RSPT_LT(I, A) launch_trace_v<ANY, OUT_MODE, I, A>(lane, count, grid, s, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, counters, xcur)
     if (s->has_instances) { if (s->has_alpha) RSPT_LT(true, true); else RSPT_LT(true, false); }
     else { if (s->has_alpha) RSPT_LT(false, true); else RSPT_LT(false, false); }
@@ -775,6 +799,8 @@ constexpr int RSPT_DL_RETRY_LANE = -1000;   // batch_direct -> the batch loop: r
 int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, void* film_dev, float* li_host, rspt_stats* stats) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
+    // ABI 23: spheres are traced (rspt_trace) but not yet shaded, textured or sampled as lights on the device: the caller keeps its CPU loop
+    if (s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with spheres: rspt_render does not serve sphere shapes yet (rspt_trace does)");
     // WhittedIntegrator::li runs on directlighting's machinery (direct.h / dl_serial.h, their WH forms) as UniformSampleAll with one estimate per light and
     // no sample arrays; max_depth 0 recurses no more than 1 does (whitted.rs:103: depth + 1 < max_depth)
     const bool whitted = d->integrator == RSPT_INTEGRATOR_WHITTED;
@@ -2062,6 +2088,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     bool has_null = false;
     const bool instanced = d->n_instances > 0;
     const uint64_t n_top_prims = instanced ? d->n_top_prims : d->n_prims, n_top_nodes = instanced ? d->n_top_nodes : d->n_nodes;
+    if (d->n_spheres && instanced) return fail(RSPT_E_UNSUPPORTED, "spheres together with object instances");   // (ABI 23: a follow-up)
     if (instanced) {  // objects + instances behind the top-level aggregate
         if (!d->instances || !d->objects || d->n_objects == 0) return fail(RSPT_E_INVALID, "instances without objects");
         if (n_top_prims > d->n_prims || n_top_nodes > d->n_nodes || n_top_nodes == 0) return fail(RSPT_E_INVALID, "bad top-level aggregate range");
@@ -2081,8 +2108,29 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             }
         }
     }
+    // ABI 23: spheres (dev_sphere.h)
+    if (d->n_spheres && !d->spheres) return fail(RSPT_E_INVALID, "null spheres with n_spheres > 0");
+    for (uint32_t i = 0; i < d->n_spheres; i++) {
+        const rspt_sphere& sp = d->spheres[i];
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(sp.object_to_world[k]) || !std::isfinite(sp.world_to_object[k])) return fail(RSPT_E_INVALID, "sphere %u: non-finite transform", i);
+        if (!(sp.radius > 0.0f) || !std::isfinite(sp.radius) || !std::isfinite(sp.z_min) || !std::isfinite(sp.z_max) || !std::isfinite(sp.phi_max) ||
+            !std::isfinite(sp.theta_min) || !std::isfinite(sp.theta_max))
+            return fail(RSPT_E_INVALID, "sphere %u: radius must be positive and finite, z / theta / phi finite", i);
+        if (sp.medium_inside > d->n_media || sp.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "sphere %u: medium index out of range", i);
+    }
     for (uint64_t i = 0; i < d->n_prims; i++) {
         const rspt_prim& p = d->prims[i];
+        if (p.mesh == RSPT_MESH_SPHERE) {
+            if (p.v[0] >= d->n_spheres) return fail(RSPT_E_INVALID, "prim %llu: sphere index out of range", (unsigned long long)i);
+            if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: material index out of range", (unsigned long long)i);
+            if (p.area_light < -1 || p.area_light >= (int64_t)d->n_lights) return fail(RSPT_E_INVALID, "prim %llu: sphere's light index out of range", (unsigned long long)i);
+            // an emissive sphere: its light is a DiffuseAreaLight on this very primitive (the pairing api.rs makes, and rspt_light.prim states)
+            if (p.area_light >= 0 && (d->lights[p.area_light].kind != RSPT_LIGHT_DIFFUSE_AREA || d->lights[p.area_light].prim != i))
+                return fail(RSPT_E_INVALID, "prim %llu: sphere's area light %d is not a DIFFUSE_AREA light on this primitive", (unsigned long long)i, p.area_light);
+            has_null |= p.material == 0xffffffffu;
+            continue;
+        }
         if (p.mesh == RSPT_MESH_INSTANCE) {
             if (!instanced || i >= n_top_prims || p.v[0] >= d->n_instances) return fail(RSPT_E_INVALID, "prim %llu: bad instance reference", (unsigned long long)i);
             continue;
@@ -2117,13 +2165,15 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     if (any_alpha)
         for (uint64_t i = 0; i < d->n_prims; i++) {
             const rspt_prim& p = d->prims[i];
-            if (p.mesh != RSPT_MESH_INSTANCE && p.mesh < d->n_meshes && p.area_light >= 0 && (d->meshes[p.mesh].alpha_tex || d->meshes[p.mesh].shadow_alpha_tex))
+            if (p.mesh < d->n_meshes && p.area_light >= 0 && (d->meshes[p.mesh].alpha_tex || d->meshes[p.mesh].shadow_alpha_tex))
                 return fail(RSPT_E_UNSUPPORTED, "prim %llu: an emissive mesh with an alpha mask", (unsigned long long)i);
         }
     for (uint32_t i = 0; i < d->n_lights; i++) {
         if (d->lights[i].kind < RSPT_LIGHT_DIFFUSE_AREA || d->lights[i].kind > RSPT_LIGHT_INFINITE) return fail(RSPT_E_UNSUPPORTED, "light %u: unsupported kind %u", i, d->lights[i].kind);
-        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->lights[i].prim >= n_top_prims || d->prims[d->lights[i].prim].mesh == RSPT_MESH_INSTANCE))
+        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->lights[i].prim >= n_top_prims || d->prims[d->lights[i].prim].mesh == RSPT_MESH_INSTANCE))   // (a sphere primitive may be named, ABI 23)
             return fail(RSPT_E_INVALID, "light %u: prim out of range", i);
+        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && d->prims[d->lights[i].prim].mesh == RSPT_MESH_SPHERE && d->prims[d->lights[i].prim].area_light != (int32_t)i)
+            return fail(RSPT_E_INVALID, "light %u: its sphere primitive names another light", i);
         if (d->lights[i].kind == RSPT_LIGHT_INFINITE && d->lights[i].prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u: envmap index out of range", i);
     }
     // textures: constant / imagemap / scale; each material may bind at most RSPT_TEX_SLOTS distinct ones
@@ -2324,7 +2374,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             std::vector<float> nuv((size_t)d->n_prims * 20, 0.0f);
             for (uint64_t i = 0; i < d->n_prims; i++) {
                 const rspt_prim& pr = d->prims[i];
-                if (pr.mesh == RSPT_MESH_INSTANCE) continue;
+                if (pr.mesh == RSPT_MESH_INSTANCE || pr.mesh == RSPT_MESH_SPHERE) continue;
                 const rspt_mesh& me = d->meshes[pr.mesh];
                 float* q = nuv.data() + 20 * i;
                 for (int k = 0; k < 3; k++) {
@@ -2569,7 +2619,8 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
         // ---- the quantised form of the records (trace_w4q.h) for the shadow rays of scenes without instances and alpha masks ----
         bool any_alpha = false;
         for (uint32_t i = 0; i < d->n_meshes; i++) any_alpha = any_alpha || d->meshes[i].alpha_tex || d->meshes[i].shadow_alpha_tex;
-        if (s->w4_ok && !recs.empty() && !instanced && !any_alpha && env_size("RSPT_W4Q_BUILD", 1) != 0) {
+        // (not for scenes with spheres either: k_trace_w4q walks triangle leaves only, and launch_trace_sph never takes it)
+        if (s->w4_ok && !recs.empty() && !instanced && !any_alpha && d->n_spheres == 0 && env_size("RSPT_W4Q_BUILD", 1) != 0) {
             std::vector<Quad4Node> q(recs.size());
             bool ok = true;
             for (size_t i = 0; i < recs.size() && ok; i++) {
@@ -2622,7 +2673,8 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     }
     if (d->n_prims) {
         float4* tris = nullptr;
-        hipError_t e = hipMalloc((void**)&tris, d->n_prims * 3 * sizeof(float4));
+        // a scene with spheres keeps them behind the triangle records (dev_sphere.h SphereDev, RSPT_SPHERE_F4 float4 each)
+        hipError_t e = hipMalloc((void**)&tris, (d->n_prims * 3 + (uint64_t)d->n_spheres * RSPT_SPHERE_F4) * sizeof(float4));
         if (e != hipSuccess) return bail(fail(RSPT_E_NOMEM, "triangle records: %s", hipGetErrorString(e)));
         s->allocs.push_back(tris);
         const uint32_t* inst_cont_d = nullptr;
@@ -2670,6 +2722,14 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
         hipLaunchKernelGGL(k_build_tris, dim3((uint32_t)((d->n_prims + 255) / 256)), dim3(256), 0, g.stream, s->dev.prims, meshes_d, P_d, (uint32_t)d->n_prims, tris, inst_cont_d, mesh_mask_d);
         e = hipStreamSynchronize(g.stream);
         if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "k_build_tris: %s", hipGetErrorString(e)));
+        if (d->n_spheres) {   // ABI 23: the sphere records behind the primitive records (dev_sphere.h SphereDev; k_build_tris wrote the sphere primitives' own records)
+            std::vector<SphereDev> sph(d->n_spheres);
+            memset(sph.data(), 0, sph.size() * sizeof(SphereDev));
+            for (uint32_t k = 0; k < d->n_spheres; k++) sph[k].s = d->spheres[k];
+            e = hipMemcpy(tris + 3 * d->n_prims, sph.data(), sph.size() * sizeof(SphereDev), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "sphere records: %s", hipGetErrorString(e)));
+            s->has_spheres = true;
+        }
         s->dev.tris = tris;
         if (s->w4_ok && s->w4 && !instanced && (!s->has_alpha || s->alpha_simple) && env_size("RSPT_SERIAL_W4", 1) != 0) {   // the per-lane kernels' traversal (trace_serial.h)
             s->dev.w4 = s->w4; s->dev.w4_big = s->big_leaves; s->dev.w4_root = s->w4_root;
@@ -2908,21 +2968,46 @@ __global__ void k_leaf_lobe(const float* __restrict__ x, uint64_t n, float* __re
     const rgb sf = lobe_sample_f<SF_ALL>(b, lt, wo, &w, f2{q[6], q[7]}, &pdf, &st, true);
     o[4] = sf.r; o[5] = sf.g; o[6] = sf.b; o[7] = w.x; o[8] = w.y; o[9] = w.z; o[10] = pdf; o[11] = (float)st; o[12] = (float)lobe_type(b.type);
 }
+// rspt_libm code 15 (ABI 23): one rspt_sphere (42 words) + o, d, t_max -> sphere_hit and sphere_test (dev_sphere.h) as the traversal calls them; 64 floats in and out
+__global__ void k_leaf_sphere(const float* __restrict__ x, uint64_t n, float* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rspt_sphere sp;
+    uint32_t* sw = reinterpret_cast<uint32_t*>(&sp);
+    for (int k = 0; k < 42; k++) sw[k] = __float_as_uint(x[64 * i + k]);
+    const float* q = x + 64 * i + 42;
+    const f3 o{q[0], q[1], q[2]}, d{q[3], q[4], q[5]};
+    float* r = out + 64 * i;
+    for (int k = 0; k < 64; k++) r[k] = 0.0f;
+    SphereHit h;
+    if (sphere_hit(sp, o, d, q[6], &h)) {
+        const f3 v[13] = {h.p, h.p_error, h.n, f3{h.u, h.v, 0.0f}, h.dpdu, h.dpdv, h.dndu, h.dndv, h.sn, h.sdpdu, h.sdpdv, h.sdndu, h.sdndv};
+        r[0] = 1.0f; r[1] = h.t;
+        int k = 2;
+        for (int j = 0; j < 13; j++) {
+            r[k++] = v[j].x; r[k++] = v[j].y;
+            if (j != 3) r[k++] = v[j].z;
+        }
+    }
+    float t = 0.0f;
+    r[43] = sphere_test(sp, o, d, q[6], &t) ? 1.0f : 0.0f;
+}
 }  // namespace
 extern "C" {
 int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* out) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (n == 0) return RSPT_OK;
-    if (fn > RSPT_LIBM_LOBE || !x || !out || (fn == RSPT_LIBM_ATAN2 && !y) || n > (fn >= RSPT_LIBM_MAT4_INVERSE ? (1ull << 27) : (1ull << 31))) return fail(RSPT_E_INVALID, "bad function, null argument or more than 2^31 values (2^27 sixteen-float elements)");
+    if (fn > RSPT_LIBM_SPHERE || !x || !out || (fn == RSPT_LIBM_ATAN2 && !y) || n > (fn >= RSPT_LIBM_MAT4_INVERSE ? (1ull << 27) : (1ull << 31))) return fail(RSPT_E_INVALID, "bad function, null argument or more than 2^31 values (2^27 sixteen-float elements)");
     HIP_TRY(hipSetDevice(g.device));
     float *xd = nullptr, *yd = nullptr, *od = nullptr;
     struct Guard { float **a, **b, **c; ~Guard() { for (float** p : {a, b, c}) if (*p) (void)hipFree(*p); } } guard{&xd, &yd, &od};
     int rc;
-    const uint64_t per = fn == RSPT_LIBM_LOBE ? 48u : (fn >= RSPT_LIBM_MAT4_INVERSE ? 16u : 1u);   // values per element
+    const uint64_t per = fn == RSPT_LIBM_SPHERE ? 64u : (fn == RSPT_LIBM_LOBE ? 48u : (fn >= RSPT_LIBM_MAT4_INVERSE ? 16u : 1u));   // values per element
     if ((rc = dev_alloc(&xd, n * per)) || (rc = dev_alloc(&od, n * per)) || (y && (rc = dev_alloc(&yd, n)))) return rc;
     HIP_TRY(hipMemcpyAsync(xd, x, n * per * sizeof(float), hipMemcpyHostToDevice, g.stream));
     if (y) HIP_TRY(hipMemcpyAsync(yd, y, n * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    if (fn == RSPT_LIBM_LOBE) hipLaunchKernelGGL(k_leaf_lobe, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, xd, n, od);
+    if (fn == RSPT_LIBM_SPHERE) hipLaunchKernelGGL(k_leaf_sphere, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, xd, n, od);
+    else if (fn == RSPT_LIBM_LOBE) hipLaunchKernelGGL(k_leaf_lobe, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, xd, n, od);
     else if (fn > RSPT_LIBM_MAT4_INVERSE) hipLaunchKernelGGL(k_leaf_geom, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, fn, xd, n, od);
     else hipLaunchKernelGGL(k_libm, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, fn, xd, yd, n, od);
     HIP_TRY(hipGetLastError());
@@ -2934,6 +3019,7 @@ int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* ou
 int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3], float* func_out, float* cdf_out, int32_t nvox_out[3], int32_t voxel_out[3]) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
+    if (s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "sphere scenes: the light distributions are not built for sphere area lights yet");
     const uint32_t nl = s->dev.n_lights;
     if (nl == 0) return fail(RSPT_E_INVALID, "the scene has no lights");
     HIP_TRY(hipSetDevice(g.device));
@@ -2985,6 +3071,7 @@ int rspt_trace_device(rspt_scene_t s, const void* rays_dev, uint64_t n, void* ou
     if (!s || (n && (!rays_dev || !out_dev))) return fail(RSPT_E_INVALID, "null argument");
     if (n > 0xfffffff0ull) return fail(RSPT_E_UNSUPPORTED, "more than 2^32 rays per call");
     if (repeat < 1) repeat = 1;
+    if (s->has_spheres && !s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "sphere scene with more four-box records than a reference holds");
     HIP_TRY(hipSetDevice(g.device));
     if (!g.totals) { int rc = dev_alloc(&g.totals, 8); if (rc) return rc; }
     const bool counters = env_size("RSPT_COUNTERS", 0) != 0;

@@ -24,6 +24,7 @@
 // Leaf refs carry (first primitive, count) so the leaf phase needs no LinearBVHNode fetch.
 #pragma once
 #include "trace_wide.h"
+#include "dev_sphere.h"
 
 namespace rspt {
 
@@ -131,8 +132,11 @@ RDEVN bool box_hit6_m(float lx, float ly, float lz, float hx, float hy, float hz
 // Msamples/s (two alternating rounds, profiles/r06_c5_anim_waves_ab.txt).  (1, 8) is the backend's own default: every other instantiation keeps the budget it was measured with.
 #define RSPT_W4_ATTR __attribute__((amdgpu_waves_per_eu((ANIM && !ANY) ? 4 : 1, (ANIM && !ANY) ? 4 : 8)))
 #endif
+// SPH (ABI 23, scenes with spheres; never with INST): a leaf record carrying MF_SPHERE is a GeometricPrimitive over a Sphere — dev_sphere.h sphere_test
+// (Sphere::intersect / intersect_p up to t_shape_hit) on the world ray, reloaded from its queue record for the direction; its t becomes the ray's t_max
+// (primitive.rs:150-156).  b0..b2 of a sphere hit are 0.  The triangle instantiations (SPH = false) compile none of it.
 template <bool ANY, int OUT_MODE, bool INST, int ALPHA /* 0: no masks, 1: alpha_pass (any texture graph, a call), 2: alpha_simple (in line) */, bool ANIM = false,
-          int BLOCK = RSPT_PW_BLOCK, int TOPCAP = RSPT_W4_TOP>
+          int BLOCK = RSPT_PW_BLOCK, int TOPCAP = RSPT_W4_TOP, bool SPH = false>
 __global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, TexTables tt, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
                                                            const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
                                                            const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
@@ -456,6 +460,20 @@ __global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, Te
                             else
 #include "trace_w4_enter.h"
                             break;
+                        }
+                        if constexpr (SPH) {
+                            if (__float_as_uint(c.w) & MF_SPHERE) {
+                                const float4* rp = reinterpret_cast<const float4*>(((entry & RSPT_Q_MIS) ? rays_b : rays_a) + (entry & ~RSPT_Q_MIS));
+                                const float4 r0 = rp[0], r1 = rp[1];
+                                const SphereDev* sp_rec = reinterpret_cast<const SphereDev*>(sc.tris + 3 * (size_t)sc.n_prims) + __float_as_uint(a.x);
+                                float ts;
+                                if (sphere_test(sp_rec->s, o, f3{r0.w, r1.x, r1.y}, t_max, &ts)) {
+                                    if (ANY) { best = 0; break; }
+                                    t_max = ts;      // primitive.rs:155
+                                    best = pi; bt = ts; bb0 = bb1 = bb2 = 0.0f;
+                                }
+                                continue;
+                            }
                         }
                         float t, b0, b1, b2;
                         if (tri_test(f3{a.x, a.y, a.z}, f3{a.w, b.x, b.y}, f3{b.z, b.w, c.x}, INST ? f3{ox, oy, oz} : o, rs, t_max, &t, &b0, &b1, &b2)) {

@@ -40,6 +40,10 @@ constexpr uint32_t SV_DYNAMIC = SF_ALL & ~SF_ANIM;                              
 #define RSPT_TU_W4B(ANY, OM, B, T) \
     RSPT_TU_X template __global__ void k_trace_w4<ANY, OM, false, 0, false, B, T>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, \
                                                                                    const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, uint32_t*, uint32_t*, uint32_t);   /* big workgroups, big LDS top */
+#define RSPT_TU_W4SPH(ANY, A) \
+    RSPT_TU_X template __global__ void k_trace_w4<ANY, 1, false, A, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, \
+                                                                  uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, \
+                                                                  uint32_t*, uint32_t*, uint32_t);   /* scenes with spheres (ABI 23): the trace hook */
 #define RSPT_TU_W4_4(ANY, OM) RSPT_TU_W4(ANY, OM, false, 0) RSPT_TU_W4(ANY, OM, false, 1) RSPT_TU_W4(ANY, OM, true, 0) RSPT_TU_W4(ANY, OM, true, 1)
 #define RSPT_TU_W4_S(ANY, OM) RSPT_TU_W4(ANY, OM, false, 2) RSPT_TU_W4(ANY, OM, true, 2)   /* alpha masks evaluated in line (alpha_simple) */
 #define RSPT_TU_REF(ANY, OM, C, I, A) \
@@ -163,6 +167,9 @@ RSPT_TU_W4_4(false, 0) RSPT_TU_W4_4(false, 1) RSPT_TU_W4_4(true, 0) RSPT_TU_W4_4
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4S)
 RSPT_TU_W4_S(false, 0) RSPT_TU_W4_S(false, 1) RSPT_TU_W4_S(true, 0) RSPT_TU_W4_S(true, 1)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4SPH)
+RSPT_TU_W4SPH(false, 0) RSPT_TU_W4SPH(false, 1) RSPT_TU_W4SPH(false, 2) RSPT_TU_W4SPH(true, 0) RSPT_TU_W4SPH(true, 1) RSPT_TU_W4SPH(true, 2)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4A)
 RSPT_TU_W4A(false, 0) RSPT_TU_W4A(false, 1) RSPT_TU_W4A(true, 0) RSPT_TU_W4A(true, 1)

@@ -495,7 +495,8 @@ class SceneBuilder:
         self.objects = {}            # name -> index
         self.cur_object = -1
         self.instances = []          # (object index, Transform primitive_to_world)
-        self.decl = []               # render_options.primitives order: ("mesh", m) | ("inst", k)
+        self.decl = []               # render_options.primitives order: ("mesh", m) | ("inst", k) | ("sphere", k)
+        self.spheres = []            # Shape "sphere" (ABI 23): (rspt_sphere record, material, emit, declaration parameters)
 
     # ---- object instancing ----
     def begin_object(self, name):  # pbrt_object_begin api.rs:3001-3013
@@ -680,6 +681,36 @@ class SceneBuilder:
         self.nv += len(P)
         return m
 
+    def add_sphere(self, radius=1.0, zmin=None, zmax=None, phimax=360.0, object_to_world=None, material=None, emit=None, two_sided=False, medium=(None, None)):
+        """Shape "sphere" (api.rs make_shapes, shapes/sphere.rs:59-84) under the CTM object_to_world (a Transform; its m_inv is world_to_object):
+        Sphere::new's clamps, acos and radians in f32 with the host libm.  zmin / zmax default to -radius / radius.  emit = rgb L makes it a
+        DiffuseAreaLight (one per sphere).  The library traces spheres (rspt_trace); rspt_render refuses scenes that hold any."""
+        assert self.cur_object < 0, "spheres inside ObjectBegin / ObjectEnd are not modelled (spheres next to object instances are refused)"
+        if material is None:
+            material = abi.NO_MATERIAL
+        xf = object_to_world if object_to_world is not None else Transform.identity()
+        r = F32(radius)
+        z0, z1 = F32(-r if zmin is None else zmin), F32(r if zmax is None else zmax)
+        lo, hi = min(z0, z1), max(z0, z1)
+        clamp = lambda v, a, b: a if v < a else (b if v > b else v)      # noqa: E731  clamp_t (pbrt.rs)
+        rec = np.zeros((), abi.SPHERE_DT)
+        rec["object_to_world"] = np.asarray(xf.m, F32).reshape(-1); rec["world_to_object"] = np.asarray(xf.m_inv, F32).reshape(-1)
+        rec["radius"] = r
+        rec["z_min"] = clamp(lo, F32(-r), r); rec["z_max"] = clamp(hi, F32(-r), r)
+        rec["theta_min"] = _libm_f32("acosf", clamp(F32(lo / r), F32(-1), F32(1)))
+        rec["theta_max"] = _libm_f32("acosf", clamp(F32(hi / r), F32(-1), F32(1)))
+        rec["phi_max"] = F32(F32(F32(math.pi) / F32(180)) * clamp(F32(phimax), F32(0), F32(360)))      # radians() pbrt.rs:143-146
+        m = np.asarray(xf.m, F32)
+        det = F32(F32(F32(m[0, 0] * F32(F32(m[1, 1] * m[2, 2]) - F32(m[1, 2] * m[2, 1]))) - F32(m[0, 1] * F32(F32(m[1, 0] * m[2, 2]) - F32(m[1, 2] * m[2, 0]))))
+                  + F32(m[0, 2] * F32(F32(m[1, 0] * m[2, 1]) - F32(m[1, 1] * m[2, 0]))))      # Transform::swaps_handedness (transform.rs:309-315)
+        rec["transform_swaps_handedness"] = int(det < 0)
+        rec["medium_inside"], rec["medium_outside"] = medium[0] or 0, medium[1] or 0
+        k = len(self.spheres)
+        self.decl.append(("sphere", k))
+        self.spheres.append((rec, material, None if emit is None else (np.array(emit, F32), bool(two_sided)),
+                             dict(radius=float(radius), zmin=float(z0), zmax=float(z1), phimax=float(phimax), xf=xf)))
+        return k
+
     def add_quad(self, p, material, **kw):
         return self.add_mesh(np.array(p, F32), [[0, 1, 2], [0, 2, 3]], material, **kw)
 
@@ -740,6 +771,8 @@ class SceneBuilder:
         With object instances the top-level aggregate is built over (top-level triangles in declaration order, then the
         TransformedPrimitives in declaration order) from their world bounds by rspt_bvh_build_bounds; every object with more
         than one triangle gets its own BVHAccel from bvh_builder (api.rs:3046-3094)."""
+        if self.spheres:
+            return self._finish_spheres(max_prims_in_node, instancing)
         P = np.ascontiguousarray(np.concatenate(self.P), F32)
         tri = np.ascontiguousarray(np.concatenate(self.tris), np.uint32)
         tri_mesh = np.concatenate(self.tri_mesh)
@@ -857,6 +890,75 @@ class SceneBuilder:
                      instancing={"reference": abi.INSTANCING_REFERENCE, "fixed": abi.INSTANCING_FIXED}[instancing], builder=self)
 
 
+    def _finish_spheres(self, max_prims_in_node, instancing):
+        """finish() of a scene with spheres (ABI 23): the aggregate's input list is render_options.primitives — every shape's primitives in
+        declaration order (a mesh's triangles, a sphere) — built from their world bounds by rspt_bvh_build_bounds: a triangle's is its three
+        vertices (Triangle::world_bound), a sphere's Sphere::world_bound = object_to_world.transform_bounds(object_bound) (sphere.rs:85-102)."""
+        from . import lib
+        assert not self.instances, "spheres together with object instances are refused by the library"
+        P = np.ascontiguousarray(np.concatenate(self.P), F32) if self.P else np.zeros((0, 3), F32)
+        tri = np.ascontiguousarray(np.concatenate(self.tris), np.uint32) if self.tris else np.zeros((0, 3), np.uint32)
+        tri_mesh = np.concatenate(self.tri_mesh) if self.tri_mesh else np.zeros(0, np.uint32)
+        first_tri_of_mesh = np.concatenate([[0], np.cumsum([len(t) for t in self.tris])]).astype(np.int64)
+        in_tri, in_sph = [], []
+        for kind, ref in self.decl:
+            if kind == "mesh":
+                nt = len(self.tris[ref])
+                in_tri.append(np.arange(first_tri_of_mesh[ref], first_tri_of_mesh[ref] + nt)); in_sph.append(np.full(nt, -1))
+            else:
+                in_tri.append(np.array([-1])); in_sph.append(np.array([ref]))
+        in_tri, in_sph = np.concatenate(in_tri).astype(np.int64), np.concatenate(in_sph).astype(np.int64)
+        bounds = np.zeros((len(in_tri), 6), F32)
+        tsel = in_tri >= 0
+        tv = P[tri[in_tri[tsel]]]
+        bounds[tsel, :3], bounds[tsel, 3:] = tv.min(1), tv.max(1)
+        for row in np.nonzero(~tsel)[0]:
+            bounds[row, :3], bounds[row, 3:] = sphere_world_bound(self.spheres[in_sph[row]][0])
+        nodes, ordered = lib.bvh_build_bounds(bounds, max_prims_in_node)
+        n = len(bounds)
+        prims = np.zeros(n, abi.PRIM_DT)
+        mesh_mat = np.array(self.mesh_material, np.uint32)
+        slot_tri, slot_sph = in_tri[ordered], in_sph[ordered]
+        ts = slot_tri >= 0
+        prims["v"][ts] = tri[slot_tri[ts]]
+        prims["mesh"][ts] = tri_mesh[slot_tri[ts]]
+        prims["material"][ts] = mesh_mat[tri_mesh[slot_tri[ts]]]
+        prims["v"][~ts, 0] = slot_sph[~ts].astype(np.uint32)
+        prims["mesh"][~ts] = abi.MESH_SPHERE
+        prims["material"][~ts] = [self.spheres[k][1] for k in slot_sph[~ts]]
+        prims["area_light"] = -1
+        # lights in shape-declaration order (one DiffuseAreaLight per emissive triangle or sphere, api.rs:2810-2852)
+        slot_of_input = np.empty(n, np.int64)
+        slot_of_input[ordered] = np.arange(n)
+        lights_in = []
+        for i in range(n):
+            emit = self.mesh_emit[tri_mesh[in_tri[i]]] if in_tri[i] >= 0 else self.spheres[in_sph[i]][2]
+            if emit is not None:
+                prims["area_light"][slot_of_input[i]] = len(lights_in)
+                lights_in.append((slot_of_input[i], emit))
+        lights = np.zeros(len(lights_in) + len(self.delta_lights), abi.LIGHT_DT)
+        for i, (slot, (L, two)) in enumerate(lights_in):
+            lights[i]["kind"] = abi.LIGHT_DIFFUSE_AREA; lights[i]["prim"] = slot; lights[i]["L"] = L; lights[i]["two_sided"] = int(two)
+        for i, lt in enumerate(self.delta_lights):
+            lights[len(lights_in) + i] = lt
+        mats = self.material_descs()
+        meshes = np.array(self.meshes, np.uint32).view(abi.MESH_DT).reshape(-1) if self.meshes else np.zeros(0, abi.MESH_DT)
+        return Scene(nodes=nodes, prims=prims, meshes=meshes, P=P,
+                     N=np.ascontiguousarray(np.concatenate(self.N), F32) if self.any_n else None,
+                     UV=np.ascontiguousarray(np.concatenate(self.UV), F32) if self.any_uv else None,
+                     materials=mats, lights=lights, envmaps=self.envmaps,
+                     textures=np.array(self.textures, abi.TEXTURE_DT) if self.textures else None, images=self.images,
+                     media=np.array(self.media, abi.MEDIUM_DT) if self.media else None,
+                     instancing={"reference": abi.INSTANCING_REFERENCE, "fixed": abi.INSTANCING_FIXED}[instancing], builder=self,
+                     spheres=np.array([sp[0] for sp in self.spheres], abi.SPHERE_DT))
+
+
+def sphere_world_bound(rec):
+    """Sphere::world_bound (sphere.rs:85-102): object_to_world.transform_bounds of ((-r, -r, z_min), (r, r, z_max))"""
+    r = F32(rec["radius"])
+    return _transform_bounds(np.asarray(rec["object_to_world"], F32).reshape(4, 4), np.array([-r, -r, rec["z_min"]], F32), np.array([r, r, rec["z_max"]], F32))
+
+
 def _transform_bounds(m, lo, hi):
     """Transform::transform_bounds (transform.rs:596-660) in f32: the eight corners through transform_point (with its divide by the homogeneous
     weight where that is not exactly 1, :490-516), union"""
@@ -877,8 +979,9 @@ class Scene:
     """Flattened scene arrays + the ctypes rspt_scene_desc pointing at them."""
 
     def __init__(self, nodes, prims, meshes, P, N, UV, materials, lights, S=None, envmaps=(), textures=None, images=(),
-                 objects=None, instances=None, n_top=None, instancing=abi.INSTANCING_REFERENCE, builder=None, media=None):
+                 objects=None, instances=None, n_top=None, instancing=abi.INSTANCING_REFERENCE, builder=None, media=None, spheres=None):
         self.media = media if media is not None else np.zeros(0, abi.MEDIUM_DT)
+        self.spheres = spheres if spheres is not None else np.zeros(0, abi.SPHERE_DT)   # ABI 23
         self.builder = builder  # declaration-order view of the scene (tools/export_pbrt.py)
         self.nodes, self.prims, self.meshes, self.P, self.N, self.UV, self.S = nodes, prims, meshes, P, N, UV, S
         self.objects = objects if objects is not None else np.zeros(0, abi.OBJECT_DT)
@@ -902,7 +1005,7 @@ class Scene:
                                   p(self.textures), len(self.textures),
                                   C.addressof(self._img_structs) if self.images else None, len(self.images),
                                   p(self.objects), len(self.objects), p(self.instances), len(self.instances),
-                                  self.n_top[0], self.n_top[1], instancing, len(self.media), p(self.media))
+                                  self.n_top[0], self.n_top[1], instancing, len(self.media), p(self.media), p(self.spheres), len(self.spheres), 0)
 
     def set_instancing(self, mode):
         """"reference" | "fixed" (rspt_scene_desc.instancing_mode); takes effect at the next DeviceScene / oracle call"""

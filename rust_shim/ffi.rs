@@ -1,11 +1,12 @@
-//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 22) one to one.
+//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 23) one to one.
 //! Uncompiled source for a maintainer (the image this repo is built in has no Rust toolchain); struct layouts are checked
 //! from the C side by tests/test_abi.py, so a mismatch here shows up as a wrong `size_of` against the table in INTEGRATION.md §2.
 #![allow(dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RSPT_ABI_VERSION: c_int = 22;
+pub const RSPT_ABI_VERSION: c_int = 23;
 pub const RSPT_MESH_INSTANCE: u32 = 0xffff_ffff;
+pub const RSPT_MESH_SPHERE: u32 = 0xffff_fffe;   // ABI 23: v[0] = index into spheres
 pub const RSPT_NO_MATERIAL: u32 = 0xffff_ffff;
 
 #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -15,6 +16,11 @@ pub struct RsptPrim { pub v: [u32; 3], pub mesh: u32, pub material: u32, pub are
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RsptMesh { pub has_n: u32, pub has_s: u32, pub has_uv: u32, pub flip: u32, pub alpha_tex: u32, pub shadow_alpha_tex: u32,
                       pub medium_inside: u32, pub medium_outside: u32 }   // 0 = none, else 1 + index into media
+/// rspt_sphere (ABI 23): what Sphere holds (shapes/sphere.rs:21-35); the two matrices are the Transform.m api.rs hands Sphere::new
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RsptSphere { pub object_to_world: [f32; 16], pub world_to_object: [f32; 16], pub radius: f32, pub z_min: f32, pub z_max: f32,
+                        pub theta_min: f32, pub theta_max: f32, pub phi_max: f32, pub reverse_orientation: u32, pub transform_swaps_handedness: u32,
+                        pub medium_inside: u32, pub medium_outside: u32 }   // 168 B
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RsptMedium { pub kind: u32, pub sigma_a: [f32; 3], pub sigma_s: [f32; 3], pub g: f32,                 // kind 1 = HomogeneousMedium
                         pub nx: i32, pub ny: i32, pub nz: i32, pub pad: u32, pub density: *const f32, pub world_to_medium: [f32; 16] }   // kind 2 = GridDensityMedium
@@ -49,6 +55,7 @@ pub struct RsptInstance { pub object: u32, pub to_world: [f32; 16], pub from_wor
     pub textures: *const RsptTexture, pub n_textures: u32, pub images: *const RsptImage, pub n_images: u32,
     pub objects: *const RsptObject, pub n_objects: u32, pub instances: *const RsptInstance, pub n_instances: u32,
     pub n_top_nodes: u64, pub n_top_prims: u64, pub instancing_mode: u32, pub n_media: u32, pub media: *const RsptMedium,
+    pub spheres: *const RsptSphere, pub n_spheres: u32, pub pad_spheres: u32,   // ABI 23
 }
 #[repr(C)] pub struct RsptSamplerTables { pub sobol32: *const u32, pub vdc: *const u64, pub vdc_inv: *const u64,
                                             pub halton_perms: *const u16, pub n_halton_perms: u64 }

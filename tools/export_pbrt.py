@@ -213,9 +213,34 @@ def export(sc, path, look_at, fov, xres, yres, spp, max_depth=5, sampler="sobol"
             if sb.mesh_object[m] == o:
                 out += mesh_block(m, "  ")
         out.append("ObjectEnd")
+    def sphere_block(k):
+        """Shape "sphere" under its own CTM: one Transform directive, so rs_pbrt derives world_to_object by Matrix4x4::inverse — the builder's
+        Transform must be Transform(m); an area light's AreaLightSource comes before the shape (api.rs make_shapes / pbrt_shape)"""
+        _rec, mat, emit, prm = sb.spheres[k]
+        from rs_pbrt_amd import scenes as _sc
+        xf = prm["xf"]
+        assert np.array_equal(np.asarray(xf.m_inv, np.float32), np.asarray(_sc.Transform(xf.m).m_inv, np.float32)), "sphere transform was not built as Transform(m)"
+        text = 'Material ""' if mat == _abi.NO_MATERIAL else sb.materials[mat].get("pbrt")
+        assert text, "material %d has no pbrt directive (textured parameter?)" % mat
+        if isinstance(text, tuple):
+            text = 'Material "mix" "string namedmaterial1" ["mat%d_1"] "string namedmaterial2" ["mat%d_2"] %s' % (mat, mat, text[3])
+        blk = ["AttributeBegin"]
+        mi, mo = int(_rec["medium_inside"]), int(_rec["medium_outside"])
+        if mi or mo:
+            blk.append('  MediumInterface "%s" "%s"' % ("medium%d" % mi if mi else "", "medium%d" % mo if mo else ""))
+        if emit is not None:
+            blk.append('  AreaLightSource "diffuse" "rgb L" [%s] "bool twosided" ["%s"]' % (f(emit[0]), "true" if emit[1] else "false"))
+        blk += ["  " + text, "  Transform [%s]" % f(np.asarray(xf.m, np.float32).reshape(4, 4).T),
+                '  Shape "sphere" "float radius" [%s] "float zmin" [%s] "float zmax" [%s] "float phimax" [%s]' % (
+                    f(prm["radius"]), f(prm["zmin"]), f(prm["zmax"]), f(prm["phimax"])),
+                "AttributeEnd"]
+        return blk
+
     for what, k in sb.decl:
         if what == "mesh":
             out += mesh_block(k)
+        elif what == "sphere":
+            out += sphere_block(k)
         else:
             obj, xf, xf_end, _times = sb.instances[k]
             from rs_pbrt_amd import scenes as _sc
