@@ -12,8 +12,11 @@ frame is fixed) and the per-rank films are summed onto rank 0 by one ncclReduce 
     python bench.py                       # N=1, 1 warm-up + 2 timed steps
     python bench.py --gpus 8              # spawns 8 ranks itself (torch.distributed.run) when WORLD_SIZE is unset
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 ... bench.py --gpus 8
+    python bench.py --full                # the headline and everything below
 
-At N = 1 the line also carries (rank 0 only, outside the timed region of the headline):
+A plain run does only what the headline needs: scene build and upload, the warm-up, the timed steps, --dump-outputs, the line.
+Its `roofline` is a stub that says it was not measured.  With --full the line also carries (roofline at every N; the rest at N = 1,
+rank 0 only; all of it outside the timed region of the headline):
   roofline       the traversal kernel (k_trace_w4, closest-hit + shadow-ray launches): its measured limiter (L1 request rate, from the
                  hash-matched PMC profile), its fabric-side traffic / the wall time of its launches against the 8 TB/s HBM peak, and
                  SURVEY 8(d)'s algorithmic bytes as a rate (not a fraction); the same for the shade stage under roofline.shade
@@ -52,10 +55,12 @@ def parse():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--instancing", default="reference", choices=["reference", "fixed"], help="c5: what a hit inside an object instance is (rspt_scene_desc.instancing_mode)")
     ap.add_argument("--moving", action="store_true", help="c5: every instance is a MOVING TransformedPrimitive (two keys that differ by a rotation; k_trace_w4<INST, ANIM>)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 line and the 1/8-frame probe")
+    ap.add_argument("--full", action="store_true", help="also the roofline (a counting pass of its own), the CPU baseline and, on the default configuration, "
+                                                        "the C3 line and the 1/8-frame probe; the --no-* switches below drop parts of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 line and the 1/8-frame probe")
     ap.add_argument("--no-count", action="store_true", help="skip the reference-order counting pass (no roofline block): for PMC runs")
-    ap.add_argument("--cpu-spp", type=int, default=16)
+    ap.add_argument("--cpu-spp", type=int, default=16, help="with --full: spp of the CPU baseline's sample of the frame")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="rank 0 writes what the last timed step computed to DIR/film.npy: the frame, float32 [pixels, 4] (xyz + filter weight), after the reduce; "
                          "a frame over 64 MB is cut to a fixed seeded sample of its pixels, whose indices go to DIR/film_pixels.npy (float64)")
@@ -428,9 +433,10 @@ def measure(args, lib, scenes, workload, steps, warmup, shard, world, reduce_in_
             film_host.copy_(film)
         return st
 
-    # counting pass (deterministic: identical counts in the timed passes) for the algorithmic-bytes roofline; rank-local, no reduce
+    # counting pass (deterministic: identical counts in the timed passes) for the algorithmic-bytes roofline; rank-local, no reduce.  A plain run
+    # without warm-up makes it too: it is the render that allocates the path buffers and loads the kernels ahead of the first timed step
     counts = None
-    if not args.no_count and args.sampler in ("sobol", "halton"):   # (the tile-serial kernel of the pixel samplers has no counting variant)
+    if not args.no_count and (args.full or warmup == 0) and args.sampler in ("sobol", "halton"):   # (the tile-serial kernel of the pixel samplers has no counting variant)
         rd_count = mk_rd(max(spp // count_spp_div, 1), shard)
         os.environ["RSPT_COUNTERS"] = "1"
         counts = lib.render_device(ds, rd_count, film.data_ptr())
@@ -556,8 +562,21 @@ def main():
 
     if rank == 0:
         default_cfg = args.tris == 1_000_000 and not args.alpha_mask and not args.moving and args.filter == "box" and not args.res and not args.spp and world == 1 and args.integrator == "path" and args.sampler == "sobol"
-        traffic, tnote, stale = measured_traffic(lib, args.workload, default_cfg)
         ms_per_step = elapsed / args.steps * 1e3
+        if args.full:
+            traffic, tnote, stale = measured_traffic(lib, args.workload, default_cfg)
+            roofline = roofline_block(m["counts"], m["count_scale"], stats, traffic, tnote, stale, ms_per_step) if (m["counts"] and stats[0]["launches_closest"] + stats[0]["launches_any"] > 0) else (
+                {"bound": "latency", "kernel": "k_tile_serial (one lane per tile: camera sample, reference-order traversal and shade_path in turn)", "achieved": None, "peak": None,
+                 "unit": None, "frac": None, "traffic": None,
+                 "note": "the pixel samplers make a tile one serial chain (DESIGN.md section 5.7): the bound is the dependent-load latency of one lane, "
+                         "not bandwidth or issue rate; what is reported is the rate next to the CPU's"} if args.sampler not in ("sobol", "halton") else
+                {"bound": "latency", "kernel": "k_lane_dl (DirectLightingIntegrator::li, one lane per camera sample: the specular tree, its light estimates and the texture stage in one kernel)",
+                 "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
+                 "note": "the per-lane form of directlighting (DESIGN.md section 5.4: textured materials / max_depth > 8 / several specular lobes of one kind); "
+                         "no separate trace launches, the reference-order traversal runs inside the lane"})
+        else:
+            roofline = {"bound": None, "kernel": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
+                        "note": "not measured: the roofline needs a counting pass of its own, which only `bench.py --full` makes"}
         out = {
             "metric": "Mpath-samples/sec (whole node)", "value": samples_per_step * args.steps / elapsed / 1e6, "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -567,15 +586,7 @@ def main():
                        "timed_region": "per step: rspt_render_device (first launch -> film complete in HBM%s) + the copy of the film to pinned host memory "
                                        "(%.1f MB): SURVEY 8(d)'s t_render, first launch -> film in host memory" % (
                                            " on rank 0 after the reduce" if world > 1 else "", scenes.n_pixels(m["rd"]) * 16 / 1e6)},
-            "roofline": roofline_block(m["counts"], m["count_scale"], stats, traffic, tnote, stale, ms_per_step) if (m["counts"] and stats[0]["launches_closest"] + stats[0]["launches_any"] > 0) else (
-                {"bound": "latency", "kernel": "k_tile_serial (one lane per tile: camera sample, reference-order traversal and shade_path in turn)", "achieved": None, "peak": None,
-                 "unit": None, "frac": None, "traffic": None,
-                 "note": "the pixel samplers make a tile one serial chain (DESIGN.md section 5.7): the bound is the dependent-load latency of one lane, "
-                         "not bandwidth or issue rate; what is reported is the rate next to the CPU's"} if args.sampler not in ("sobol", "halton") else
-                {"bound": "latency", "kernel": "k_lane_dl (DirectLightingIntegrator::li, one lane per camera sample: the specular tree, its light estimates and the texture stage in one kernel)",
-                 "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
-                 "note": "the per-lane form of directlighting (DESIGN.md section 5.4: textured materials / max_depth > 8 / several specular lobes of one kind); "
-                         "no separate trace launches, the reference-order traversal runs inside the lane"}),
+            "roofline": roofline,
             "stats": {k: sum(s_[k] for s_ in stats) / len(stats) for k in ("t_trace_closest_s", "t_trace_any_s", "t_trace_s", "t_shade_s", "t_kernels_s", "trace_launches", "truncated_paths", "nan_samples")},
             "setup_s": {"scene_and_bvh_build": m["t_scene"], "upload": m["t_upload"], "bvh_builder": "rspt_bvh_build_gpu (device, bit-identical to BVHAccel::new)"},
         }
@@ -584,13 +595,13 @@ def main():
             out["baseline"] = ("%.2f Msamples/s = 500 * 500 * 8 samples / (1024 tiles / 1828.38 tiles/s): the reference's console transcript of this very render on 28 threads of an unnamed CPU "
                                "(docs/source/getting_started.rst:161-175; BASELINE.md section 1) — the only rate the reference publishes" % PUBLISHED_CORNELL_MSAMPLES)
         pyoracle = None
-        if world == 1 and not args.no_cpu_baseline:  # the CPU baseline is reported on rank 0 at N = 1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:  # the CPU baseline is reported on rank 0 at N = 1 only
             from oracle import pyoracle  # CPU baseline leg only
             rd0 = m["rd"]
             cx, cy = (rd0.crop_px[0] + rd0.crop_px[2]) // 2, (rd0.crop_px[1] + rd0.crop_px[3]) // 2
             fx, fy = float(rd0.full_res[0]), float(rd0.full_res[1])
             out["cpu_baseline"] = cpu_baseline(args, pyoracle, m["sc"], m["mk_rd"], args.cpu_spp, ((cx - 128) / fx, (cx + 128) / fx, (cy - 128) / fy, (cy + 128) / fy))
-        if world == 1 and not args.no_extra and args.workload == "soup1m" and default_cfg:
+        if world == 1 and args.full and not args.no_extra and args.workload == "soup1m" and default_cfg:
             extra = {}
             # what the ranks of an 8-GPU node render: every shard (r, 8, tile_chunk) of the same frame on this one GPU, same kernels, no reduce;
             # the slowest shard bounds the 8-GPU frame time (static deal of interleaved Morton chunks: how even is it?)

@@ -757,6 +757,30 @@ def test_bench_two_ranks_share_one_device(tmp_path):
     assert f1[:, 3].min() > 0
 
 
+def test_bench_full_adds_the_roofline_to_the_plain_line(tmp_path):
+    """a plain `python bench.py` makes no counting pass and prints a stub roofline; `--full` measures it.  Both time the same frame."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    common = ["--workload", "cornell", "--res", "96", "--spp", "4", "--steps", "1", "--warmup", "1", "--watchdog", "400"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, bench, "--dump-outputs", str(tmp_path / name)] + common + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        js = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, r.stdout
+        lines[name] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["samples_per_step"] == full["config"]["samples_per_step"] == 96 * 96 * 4
+    assert plain["roofline"]["bound"] is None and "--full" in plain["roofline"]["note"] and "cpu_baseline" not in plain and "extra" not in plain
+    assert full["roofline"]["kernel"].startswith("k_trace_w4") and full["roofline"]["nodes_per_ray"] > 0
+    f1, f2 = np.load(tmp_path / "plain" / "film.npy"), np.load(tmp_path / "full" / "film.npy")
+    assert np.array_equal(f1[:, 3], f2[:, 3]) and np.allclose(f1, f2, rtol=1e-6, atol=1e-7)
+
+
 def test_spatial_light_distribution_on_demand_voxels(gpu, oracle):
     """the spatial distribution is built voxel by voxel as paths look voxels up (what the reference's lazily filled hash
     table does, lightdistrib.rs:297-384) once the full table would be large; a voxel's distribution is a pure function of

@@ -11,7 +11,7 @@ tail -2 $out/pytest.log
 timeout 120 python tools/reference_pin_gpu.py > $out/reference_pin_gpu.txt 2>&1   # the product against the reference's own PNGs
 SKIP_C5=${SKIP_C5-1} bash tools/refresh_profiles.sh $tag all > $out/refresh.log 2>&1
 bash tools/collect_profiles.sh $tag $round > /dev/null 2>&1
-timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_final.json 2> $out/bench_final.err
+timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_final.json 2> $out/bench_final.err
 # the N > 1 path where the box has the devices for it: two ranks, one device each, the film reduce on the library's RCCL communicator
 if [ "$(python3 -c 'import torch; print(torch.cuda.device_count())' 2>/dev/null)" -ge 2 ] 2>/dev/null; then
   timeout 300 python3 bench.py --gpus 2 --steps 5 --warmup 2 > $out/bench_2gpu.json 2> $out/bench_2gpu.err; echo "2-GPU bench rc=$?"

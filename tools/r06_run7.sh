@@ -11,4 +11,4 @@ for i in directlighting volpath; do
   for q in 0 1; do echo "statue $i any_q=$q: $(RSPT_ANY_Q=$q timeout 300 python bench.py --workload statue --integrator $i --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-count 2>/dev/null | grep -o '"value": [0-9.]*' | head -1)"; done
   for q in 0 1; do echo "soup1m $i any_q=$q: $(RSPT_ANY_Q=$q timeout 300 python bench.py --workload soup1m --integrator $i --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-count 2>/dev/null | grep -o '"value": [0-9.]*' | head -1)"; done
 done 2>&1 | tee $out/other_integrators.txt
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; tail -c 1500 $out/bench_default.json
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; tail -c 1500 $out/bench_default.json

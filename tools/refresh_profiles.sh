@@ -1,14 +1,14 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun): bench lines, rocprofv3 kernel stats and the PMC passes behind profiles/.
 # usage: tools/refresh_profiles.sh <tag> [quick|pmc|all]  -> gpurun_out/<tag>/
-#   quick: the default bench line (with the C3 extra) + kernel stats of C2 and C3
+#   quick: the --full bench line (with the C3 extra) + kernel stats of C2 and C3
 #   pmc:   quick + the PMC passes (FETCH_SIZE / WRITE_SIZE / TCP / SQ, each in its own run, --kernel-trace only) -> pmc_traffic.json, pmc_trace_l1.md
 #   all:   pmc + the bench lines of the other workloads
 # Copy what is to be judged from gpurun_out/<tag>/ into profiles/ (tools/collect_profiles.sh <tag> r02).
 set -u
 tag=${1:-r02}; mode=${2:-quick}; out=$PWD/gpurun_out/$tag; mkdir -p $out; repo=$PWD
 export TMPDIR=/tmp
-timeout 600 python bench.py > $out/bench_soup1m.json 2> $out/bench_soup1m.err
+timeout 600 python bench.py --full > $out/bench_soup1m.json 2> $out/bench_soup1m.err
 for w in soup1m statue; do
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $out/ks_$w -- python $repo/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $out/ks_$w.log 2>&1)
   python tools/rocprof_summary.py $out/ks_$w $out/ks_$w.md "bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-extra" > /dev/null 2>&1
@@ -35,15 +35,15 @@ if [ "$mode" != quick ]; then
 fi
 if [ "$mode" = all ]; then
   for w in cornell cornell_docs statue_tex c4; do
-    timeout 300 python bench.py --workload $w --no-extra > $out/bench_$w.json 2> $out/bench_$w.err
+    timeout 300 python bench.py --full --workload $w --no-extra > $out/bench_$w.json 2> $out/bench_$w.err
   done
-  timeout 200 python bench.py --workload cornell --integrator ao --spp 16 --no-extra > $out/bench_cornell_ao.json 2> $out/bench_cornell_ao.err
-  timeout 200 python bench.py --workload cornell --integrator directlighting --no-extra > $out/bench_cornell_directlighting.json 2> $out/bench_cornell_directlighting.err
-  timeout 200 python bench.py --workload cornell --integrator volpath --no-extra > $out/bench_cornell_volpath.json 2> $out/bench_cornell_volpath.err
+  timeout 200 python bench.py --full --workload cornell --integrator ao --spp 16 --no-extra > $out/bench_cornell_ao.json 2> $out/bench_cornell_ao.err
+  timeout 200 python bench.py --full --workload cornell --integrator directlighting --no-extra > $out/bench_cornell_directlighting.json 2> $out/bench_cornell_directlighting.err
+  timeout 200 python bench.py --full --workload cornell --integrator volpath --no-extra > $out/bench_cornell_volpath.json 2> $out/bench_cornell_volpath.err
   # directlighting over textured materials: the per-lane form under Sobol' (lane_serial.h), one lane per camera sample
-  timeout 300 python bench.py --workload statue_tex --integrator directlighting --spp 64 --steps 2 --warmup 1 --cpu-spp 4 --no-extra > $out/bench_statue_tex_directlighting.json 2> $out/bench_statue_tex_directlighting.err
-  timeout 300 python bench.py --workload cornell --sampler 02sequence --steps 2 --warmup 1 --no-extra > $out/bench_cornell_02sequence.json 2> $out/bench_cornell_02sequence.err
-  timeout 300 python bench.py --workload statue --sampler 02sequence --spp 16 --steps 1 --warmup 1 --cpu-spp 4 --no-extra > $out/bench_statue_02sequence.json 2> $out/bench_statue_02sequence.err
+  timeout 300 python bench.py --full --workload statue_tex --integrator directlighting --spp 64 --steps 2 --warmup 1 --cpu-spp 4 --no-extra > $out/bench_statue_tex_directlighting.json 2> $out/bench_statue_tex_directlighting.err
+  timeout 300 python bench.py --full --workload cornell --sampler 02sequence --steps 2 --warmup 1 --no-extra > $out/bench_cornell_02sequence.json 2> $out/bench_cornell_02sequence.err
+  timeout 300 python bench.py --full --workload statue --sampler 02sequence --spp 16 --steps 1 --warmup 1 --cpu-spp 4 --no-extra > $out/bench_statue_02sequence.json 2> $out/bench_statue_02sequence.err
   # round 4, second half: the configurations scene files actually use — one line each, no CPU legs
   : > $out/variants.txt
   variant() {  # <name> <bench.py args...>
@@ -64,7 +64,7 @@ if [ "$mode" = all ]; then
   # their CPU legs instead (six minutes each, most of it scene generation)
   if [ -z "${SKIP_C5:-}" ]; then
     if [ -n "${FULL_C5:-}" ]; then
-      for m in fixed reference; do timeout 600 python bench.py --workload c5 --instancing $m --steps 3 --warmup 1 --no-extra > $out/bench_c5_$m.json 2> $out/bench_c5_$m.err; done
+      for m in fixed reference; do timeout 600 python bench.py --full --workload c5 --instancing $m --steps 3 --warmup 1 --no-extra > $out/bench_c5_$m.json 2> $out/bench_c5_$m.err; done
     else
       timeout 900 python tools/c5_both_modes.py 3 > $out/c5_both_modes.txt 2> $out/c5_both_modes.err
     fi
