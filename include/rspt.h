@@ -87,10 +87,13 @@ typedef struct {
  * z_max, theta_min, theta_max and phi_max (radians) as Sphere::new (sphere.rs:59-84) left them (the clamps and acos already applied).
  * The library intersects them exactly as Sphere::intersect / intersect_p (sphere.rs:103-360): transform_ray_with_error, the EFloat
  * quadratic with its f64 discriminant, the bound tests against t_max and 0, the z / phi clipping with the retry on t1.  A hit's t is
- * t_shape_hit.v.  Served today: rspt_trace / rspt_trace_device and RSPT_LIBM_SPHERE.  rspt_render answers RSPT_E_UNSUPPORTED ("sphere")
- * for a scene with spheres (the shading, texture and area-light stages are not built for them yet): the caller keeps its CPU loop.
- * rspt_light_distribution answers the same.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED, "sphere"): spheres together with object
- * instances.  A DIFFUSE_AREA rspt_light may name a sphere primitive (rendering it is the follow-up). */
+ * t_shape_hit.v.  Served: rspt_trace / rspt_trace_device, RSPT_LIBM_SPHERE, and rspt_render of spheres as SURFACES (hit, shaded, textured,
+ * blocking light) under RSPT_INTEGRATOR_PATH and RSPT_INTEGRATOR_AO with the Sobol' / Halton samplers; rspt_light_distribution serves a
+ * sphere scene whose spheres are no lights.  rspt_render answers RSPT_E_UNSUPPORTED ("sphere" and what is missing) for a scene with an
+ * emissive sphere (sphere area lights: rspt_light_distribution answers the same), for the directlighting / whitted / volpath integrators
+ * and the pixel samplers, and for a sphere scene whose spatial light table is too large to build up front (more bytes than
+ * RSPT_LIGHT_TABLE_EAGER_BYTES, 1 GiB by default: many thousand lights; the on-demand voxels find a hit's voxel from triangle barycentrics):
+ * the caller keeps its CPU loop.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED, "sphere"): spheres together with object instances.  A DIFFUSE_AREA rspt_light may name a sphere primitive (rendering it is the follow-up). */
 typedef struct {
     float object_to_world[16];
     float world_to_object[16];

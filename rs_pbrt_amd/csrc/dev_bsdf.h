@@ -29,9 +29,14 @@ enum : uint32_t {
     SF_DYNAMIC = 1u << 22,     // materials whose lobe list is built per hit (material_assembly.h build_part)
     SF_SOBOL = 1u << 24,       // the Sobol' sampler; an instantiation with SF_HALTON and without this bit serves Halton renders only (no Sobol' block, no LDS tables)
     SF_ANIM = 1u << 23,        // moving object instances (dev_scene.h inst_at): only the all-features instantiation carries the interpolation
+    SF_SPHERE = 1u << 25,      // analytic spheres (dev_sphere.h): a hit record with MF_SPHERE builds its Hit from sphere_hit
+    SF_TRIS_ONLY = 1u << 26,   // never a scene's need: set in every feature set built before spheres (SV_GENERIC, SV_DYNAMIC and SF_ALL derive from SF_ALL
+                               // and so carry SF_SPHERE too); a set compiles the sphere arm only with SF_SPHERE and WITHOUT this bit (shade_sph)
     SF_ALL = 0xffffffffu
 };
 #define RSPT_SF_LOBE(T) (1u << (T))
+// does instantiation F carry the sphere arm?  Only the sphere variants (tu_decl.h SV_*_SPH) do: the triangle sets keep their code and figures
+constexpr bool shade_sph(uint32_t F) { return (F & SF_SPHERE) && !(F & SF_TRIS_ONLY); }
 
 // trigonometry in the shading frame, reflection.rs:1801-1886
 RDEV float cos2_t(f3 w) { return w.z * w.z; }

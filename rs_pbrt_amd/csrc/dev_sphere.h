@@ -1,7 +1,7 @@
 // Analytic spheres (ABI 23): Sphere::intersect / intersect_p (src/shapes/sphere.rs:103-360) over EFloat (src/core/efloat.rs) and
 // Transform::transform_ray_with_error (src/core/transform.rs:793-814), operation by operation in f32 (the discriminant in f64), uncontracted
-// like the rest of the library.  The traversal kernels call sphere_test (t only); the stage hook RSPT_LIBM_SPHERE calls sphere_hit, which
-// also builds the SurfaceInteraction and transforms it to world space (transform.rs:815-860).
+// like the rest of the library.  The traversal kernels call sphere_test (t only); the stage hook RSPT_LIBM_SPHERE and the shade / texture /
+// AO stages (kernels.h sphere_fill) call sphere_hit, which also builds the SurfaceInteraction and transforms it to world space (transform.rs:815-860).
 //
 // Device layout: a scene with spheres keeps them behind its 48-byte triangle records in the same buffer (SceneDev::tris), 176 bytes each
 // (rspt_sphere + 8 bytes of padding), so that no kernel signature and no SceneDev field changes.  A sphere primitive's record carries the

@@ -10,9 +10,40 @@
 // workgroup and queue (K7, in k_shade).
 #pragma once
 #include "dev_texture.h"
+#include "dev_sphere.h"
 #include "pixel_sampler.h"
 
 namespace rspt {
+
+// ---- analytic spheres behind the trace stage (the sphere variants only: dev_bsdf.h shade_sph) ----
+// The trace stage leaves (prim, t, 0, 0) for a sphere hit; the interaction is recomputed here by sphere_hit on the world ray with the ray's
+// OWN t_max.  That is the interaction the traversal found: sphere_core picks its root (t0; t1 when t0.lo <= 0 or t0's point is clipped away)
+// from the quadratic and the clipping alone, and t_max only ever rejects (t0.hi > t_max, t1.hi > t_max).  The traversal accepted this root
+// under a t_max no larger than the ray's own (its closest hit so far), so every rejection test passes again, the same branches are taken and
+// the same root, point and phi come out, operation for operation.
+RDEV const rspt_sphere& sphere_of(const SceneDev& sc, const TriRec& t) {
+    return (reinterpret_cast<const SphereDev*>(sc.tris + 3 * (size_t)sc.n_prims) + __float_as_uint(t.p0.x))->s;   // (t0.x = sphere index, dev_sphere.h)
+}
+// Hit (and SurfaceInteraction.wo) of a sphere record: p and p_err of transform_surface_interaction, n never flipped (the shape handed to
+// SurfaceInteraction::new is None), the shading block's n and dpdu, material and area light from the primitive's record
+RDEVN void sphere_fill(const SceneDev& sc, const TriRec& t, f3 o, f3 d, float t_max, Hit* h, f3* wo, SphereHit* out = nullptr) {
+    const rspt_sphere& s = sphere_of(sc, t);
+    SphereHit sh;
+    sphere_hit(s, o, d, t_max, &sh);
+    h->p = sh.p; h->p_err = sh.p_error; h->n = sh.n;
+    h->sh_n = sh.sn; h->sh_dpdu = sh.sdpdu;
+    h->material = t.material; h->area_light = t.area_light;
+    // wo = -(object ray).d (sphere.rs:253), transformed back and normalised by transform_surface_interaction (transform.rs:826)
+    if (wo) *wo = normalize(xf_vector(s.object_to_world, -xf_vector(s.world_to_object, d)));
+    if (out) *out = sh;
+}
+// the texture stage's interaction of a sphere hit: uv, dpdu / dpdv, the shading block with dndu / dndv (Material::bump), p (the 3-D and
+// spherical / cylindrical / planar mappings)
+RDEV void sphere_texhit(const SphereHit& sh, TexHit* h) {
+    h->p = sh.p; h->n = sh.n; h->uv = f2{sh.u, sh.v};
+    h->dpdu = sh.dpdu; h->dpdv = sh.dpdv;
+    h->sh_n = sh.sn; h->sh_dpdu = sh.sdpdu; h->sh_dpdv = sh.sdpdv; h->sh_dndu = sh.sdndu; h->sh_dndv = sh.sdndv;
+}
 
 // ---- per-path state, SoA by path slot ------------------------------------------------------
 enum : uint32_t {
@@ -574,8 +605,13 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
         rgb beta{bb.x, bb.y, bb.z};
         TriRec tri = load_tri(sc, prim);
         Hit h;
-        tri_fill<(F & SF_VERTEX) != 0>(sc, prim, tri, hc.y, hc.z, hc.w, &h);
+        if constexpr (shade_sph(F)) {
+            if (!(tri.flags & MF_SPHERE)) tri_fill<(F & SF_VERTEX) != 0>(sc, prim, tri, hc.y, hc.z, hc.w, &h);
+        } else
+            tri_fill<(F & SF_VERTEX) != 0>(sc, prim, tri, hc.y, hc.z, hc.w, &h);
         f3 wo = -ray_d;  // SurfaceInteraction.wo, not normalised (triangle.rs:334)
+        if constexpr (shade_sph(F))
+            if (tri.flags & MF_SPHERE) sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &h, &wo);   // (the ray's own t_max: see sphere_fill)
         if ((F & SF_INST) && pb.hit_inst) {  // the hit lies inside an object instance: TransformedPrimitive::intersect (primitive.rs:216-253)
             const uint32_t hi = pb.hit_inst[p];
             const bool moving = (F & SF_ANIM) && hi && sc.inst[hi - 1u].anim != RSPT_MISS;   // (rare: the interpolated Transform of the path's time, as the traversal used it)
@@ -873,6 +909,8 @@ RDEVN void texture_hit_call(const SceneDev& sc, const TexTables& tt, TexHit& h, 
 // The stage for ONE hit: p = the slot that holds the hit record, its ray, the instance word and the result rows; smp = the camera sample's slot (film position, sampler
 // index: the same slot for the path integrator, slot / H for directlighting's node slots); tix = index of the ray's time (moving instances); with_diff: the ray is the camera
 // ray itself (bounce rays and rays re-spawned behind a null material carry no differentials)
+// SPH: the scene has spheres (k_texture_sph): a sphere record's TexHit comes from sphere_hit on the path's ray (sphere_fill)
+template <bool SPH = false>
 RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev& rd, const PathBuf& pb, uint32_t p, uint32_t smp, uint32_t tix, bool with_diff, const f3* lens) {
     const float4 hc = pb.hit_cont[p];
     const uint32_t prim = __float_as_uint(hc.x);
@@ -881,7 +919,18 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
     const uint32_t mf = tt.mat_flags[tri.material];
     if (!mf) return;
     TexHit h;
-    tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
+    if constexpr (SPH) {
+        if (tri.flags & MF_SPHERE) {
+            const float4* rp = reinterpret_cast<const float4*>(pb.ray_cont + p);
+            const float4 r0 = rp[0], r1 = rp[1];
+            Hit hh;
+            SphereHit sh;
+            sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, f3{r0.w, r1.x, r1.y}, r1.z, &hh, nullptr, &sh);
+            sphere_texhit(sh, &h);
+        } else
+            tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
+    } else
+        tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
     if (pb.hit_inst) {
         const uint32_t hi = pb.hit_inst[p];
         if (hi && sc.inst[hi - 1u].anim != RSPT_MISS) {   // a moving instance: its Transform at the path's time (inst_at)
@@ -917,13 +966,14 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
     }
     texture_hit(sc, tt, h, s, tri.material, pb.tex + p, pb.tex_stride);
 }
+template <bool SPH = false>
 RDEVN void texture_path(const SceneDev& sc, const TexTables& tt, const RenderDev& rd, const PathBuf& pb, uint32_t p, const f3* lens) {
     const uint32_t st = pb.state[p];
     if (!(st & ST_ALIVE)) return;
     const uint32_t prim = __float_as_uint(pb.hit_cont[p].x);
     const uint32_t bounces = (st >> ST_BOUNCE_SHIFT) & 0xffu;
     if (prim == RSPT_MISS || bounces >= rd.max_depth) return;
-    texture_slot(sc, tt, rd, pb, p, p, p, bounces == 0 && !(st & ST_NO_DIFF) /* the camera ray itself (a null-material pass-through re-spawns without differentials) */, lens);
+    texture_slot<SPH>(sc, tt, rd, pb, p, p, p, bounces == 0 && !(st & ST_NO_DIFF) /* the camera ray itself (a null-material pass-through re-spawns without differentials) */, lens);
 }
 
 // ---- K7b: bin the active queue by what the shade stage will do with each path -------------------------------------------
@@ -953,6 +1003,15 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) RSPT_TEX_OCC void k_texture(SceneDev sc
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const uint32_t p = q_sorted ? q_sorted[i] : q_active[i];
         if (p != RSPT_BIN_INVALID) [[clang::always_inline]] texture_path(sc, tt, rd, pb, p, nullptr);
+    }
+}
+// the same stage for scenes with spheres (their records build the interaction from sphere_hit); k_texture keeps its code
+RSPT_PLAIN_KERNEL __launch_bounds__(256) RSPT_TEX_OCC void k_texture_sph(SceneDev sc, TexTables tt, RenderDev rd, PathBuf pb, const uint32_t* __restrict__ q_active,
+                                                     const uint32_t* __restrict__ count_in, const uint32_t* __restrict__ q_sorted, const BinInfo* __restrict__ bi) {
+    const uint32_t n = q_sorted ? bi->total : *count_in;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t p = q_sorted ? q_sorted[i] : q_active[i];
+        if (p != RSPT_BIN_INVALID) [[clang::always_inline]] texture_path<true>(sc, tt, rd, pb, p, nullptr);
     }
 }
 RDEV uint32_t bin_key(const SceneDev& sc, const PathBuf& pb, uint32_t max_depth, uint32_t p) {
@@ -1180,8 +1239,9 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_move_flush(PathBuf pb, const uin
 // halton.rs:260-272) -> n shadow rays.  Ray k of path i sits at ray_sh[i * n + k]; its id field carries the
 // term dot(wi, n) / (pdf * n) that stage 2 adds when the ray is unoccluded.
 #define RSPT_AO_SKIP 0xffffffffu  // id of a ray that is not traced (pdf == 0)
-template <bool ANIM>   // ANIM: the scene has moving instances (their Transform at the camera sample's time, inst_at)
-__global__ __launch_bounds__(256) void k_ao_spawn(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
+// ANIM: the scene has moving instances (their Transform at the camera sample's time, inst_at); SPH: the scene has spheres (sphere_fill)
+template <bool ANIM, bool SPH>
+__device__ __forceinline__ void ao_spawn(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
                                                   uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= bt.n) return;
@@ -1194,9 +1254,15 @@ __global__ __launch_bounds__(256) void k_ao_spawn(SceneDev sc, RenderDev rd, Bat
     const f3 ray_d{r0.w, r1.x, r1.y};
     const TriRec tri = load_tri(sc, prim);
     TexHit h;  // the full interaction: li needs the geometric dpdu, not the shading one
-    tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
     Hit hp;    // p_error for spawn_ray
-    tri_fill(sc, prim, tri, hc.y, hc.z, hc.w, &hp);
+    if (SPH && (tri.flags & MF_SPHERE)) {
+        SphereHit sh;
+        sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &hp, nullptr, &sh);
+        sphere_texhit(sh, &h);
+    } else {
+        tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
+        tri_fill(sc, prim, tri, hc.y, hc.z, hc.w, &hp);
+    }
     if (pb.hit_inst) {
         const uint32_t hi = pb.hit_inst[i];
         InstDev moved{};   // (a moving instance: its Transform at the camera sample's time)
@@ -1237,6 +1303,15 @@ __global__ __launch_bounds__(256) void k_ao_spawn(SceneDev sc, RenderDev rd, Bat
         store_ray(out + k, offset_ray_origin(hp.p, hp.p_err, hp.n, wi), wi, pdf != 0.0f ? RSPT_INF : 0.0f, id);
         q_any[base + k] = i * n_samples + k;
     }
+}
+template <bool ANIM>
+__global__ __launch_bounds__(256) void k_ao_spawn(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
+                                                  uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {
+    ao_spawn<ANIM, false>(sc, rd, bt, pb, pix_list, n_samples, cos_sample, q_any, cnt);
+}
+RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_ao_spawn_sph(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
+                                                  uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {   // scenes with spheres (never with instances)
+    ao_spawn<false, true>(sc, rd, bt, pb, pix_list, n_samples, cos_sample, q_any, cnt);
 }
 // Stage 2: l += Spectrum::new(term) for the unoccluded rays, in array order (ao.rs:86-91)
 RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_ao_resolve(Batch bt, PathBuf pb, uint32_t n_samples) {

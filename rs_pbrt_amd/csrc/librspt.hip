@@ -261,7 +261,8 @@ struct rspt_scene_s {
     std::vector<uint64_t> image_base; // per image: its first float in the texel pool
     bool has_instances = false;       // object instances: two-level traversal (kernels.h traverse<ANY, true>)
     bool has_animated = false;        // ... some of them moving (dev_scene.h inst_at): the reference-order kernel serves the scene, `path` under Sobol' / Halton only
-    bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); served by the trace hook, refused by rspt_render
+    bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); rspt_render serves them under path / ao (Sobol', Halton)
+    bool has_sphere_light = false;    // an emissive sphere: refused by rspt_render and the light-distribution hook (sphere area lights are not on the device)
     std::map<int, LightDist> light_dists;  // by effective strategy
 };
 
@@ -709,24 +710,30 @@ void launch_trace_v(int lane, bool count, uint32_t grid, const rspt_scene_s* s, 
     if (trace_can_overflow(s))
         hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, n_overflow, ovf, ra, rb, oa, ob, occ, hits, hi);
 }
-// Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> on the main stream with every spill row (a non-instanced four-box walk cannot then
-// overflow, so no k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q
-// walks triangle leaves only), no big-workgroup shapes: RSPT_COUNTERS, RSPT_TRACE_KERNEL, RSPT_ANY_Q, RSPT_W4_SHAPE and RSPT_W4_SPILL_ROWS do not
-// apply.  rspt_trace_device checks w4_ok first.
-template <bool ANY>
-void launch_trace_sph(const rspt_scene_s* s, uint32_t n, uint32_t* cursor, const rspt_ray* rays, rspt_hit* hits, uint32_t* xcur) {
+// Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> with every spill row (a non-instanced four-box walk cannot then overflow, so no
+// k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q walks triangle
+// leaves only, and tune_any never measures them), no big-workgroup shapes: RSPT_COUNTERS, RSPT_TRACE_KERNEL, RSPT_ANY_Q, RSPT_W4_SHAPE and
+// RSPT_W4_SPILL_ROWS do not apply.  OUT_MODE 1 is the trace hook (main stream); OUT_MODE 0 the render's queues, on the stream the caller's lane
+// names with that lane's overflow list and spill rows (the two-stream shadow-ray overlap, RSPT_TRACE_STREAMS).  rspt_trace_device and
+// rspt_render check w4_ok first; rspt_render refuses RSPT_COUNTERS on sphere scenes.
+template <bool ANY, int OUT_MODE>
+void launch_trace_sph(int lane, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
+                      const rspt_ray* ra, const rspt_ray* rb, float4* oa, float4* ob, uint32_t* occ, rspt_hit* hits, uint32_t* xcur) {
     const SceneDev& sc = s->dev;
+    hipStream_t stream = lane ? g.stream2 : g.stream;
+    uint32_t* ovf = g.ovf + (lane ? 2 * g.ovf_cap / 3 : 0);
+    uint2* spill = g.spill + (lane ? g.spill_threads * RSPT_W4_SPILL : 0);
     const uint32_t pgrid = hinted_grid(pw_grid(), RSPT_PW_BLOCK);
     const int pw_refill = (int)env_size("RSPT_PW_REFILL", RSPT_PW_REFILL), pw_leaf = (int)env_size("RSPT_PW_LEAF", RSPT_PW_LEAF);
     const uint32_t pw_chunk = (uint32_t)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_CHUNK", RSPT_PW_CHUNK) & ~(size_t)63, 64), 1u << 20);
     uint32_t* n_overflow = cursor + 2;
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, g.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, nullptr, nullptr, n, cursor,
-                           rays, rays, nullptr, nullptr, nullptr, hits, n_overflow, g.ovf, g.spill, (uint32_t)RSPT_W4_SPILL, pw_refill, pw_leaf, s->w4_top, nullptr, xcur, pw_chunk);
+        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
+                           ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, (uint32_t)RSPT_W4_SPILL, pw_refill, pw_leaf, s->w4_top, nullptr, xcur, pw_chunk);
     };
-    if (!s->has_alpha) go(k_trace_w4<ANY, 1, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
-    else if (s->alpha_simple) go(k_trace_w4<ANY, 1, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
-    else go(k_trace_w4<ANY, 1, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    if (!s->has_alpha) go(k_trace_w4<ANY, OUT_MODE, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else go(k_trace_w4<ANY, OUT_MODE, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
 }
 template <bool ANY, int OUT_MODE>
 void launch_trace(int lane, bool count, uint32_t grid, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
@@ -735,8 +742,8 @@ void launch_trace(int lane, bool count, uint32_t grid, const rspt_scene_s* s, co
     // OFF by default: measured neutral to slightly negative (C2 474.0 -> 471.5 Msamples/s, C3 stand-in 2015.6 -> 2014.7; L2 hit rate of the closest-hit
     // launches 0.624 -> 0.620 by TCC_HIT / TCC_MISS — profiles/r05_xcd_affine_ab.txt): the tree's L2 hits are its root side, which every XCD holds anyway
     uint32_t* xcur = (xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? xcd_cursors : nullptr;
-    if (s->has_spheres) {   // ABI 23: the sphere instantiations (trace_w4.h SPH) — the hook's output mode only (rspt_render refuses sphere scenes before any launch)
-        if constexpr (OUT_MODE == 1) launch_trace_sph<ANY>(s, count_imm, cursor, ra, hits, xcur);
+    if (s->has_spheres) {   // ABI 23: the sphere instantiations (trace_w4.h SPH)
+        launch_trace_sph<ANY, OUT_MODE>(lane, s, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, xcur);
         return;
     }
 #define RSPT_LT(I, A) launch_trace_v<ANY, OUT_MODE, I, A>(lane, count, grid, s, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, counters, xcur)
@@ -775,13 +782,22 @@ const ShadeVariant g_shade_variants[] = {
     {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>},
     {SV_DYNAMIC, "dynamic", k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, 0, nullptr},   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
     {SF_ALL, "moving", k_shade<SF_ALL>, k_shade<SF_ALL>, k_shade<SF_ALL>, 0, nullptr},                     // + moving object instances (dev_scene.h inst_at)
+    // scenes with analytic spheres (SF_SPHERE; Sobol' and Halton): the generic / dynamic sets with the sphere arm (dev_bsdf.h shade_sph).  Only
+    // sphere scenes take them and sphere scenes take nothing else.  No MOVE form: sphere scenes keep slots for life (the recomputation reads the
+    // path's ray by slot).  As compiled: generic-sphere 224 VGPRs, 16 B of scratch, 2 waves / SIMD (generic: 221, 16 B, 2); dynamic-sphere 256 VGPRs
+    // + 1 AGPR, 320 B of scratch, ONE wave / SIMD (dynamic: 223, 304 B, 2) — a sphere scene with a dynamic material (a lobe list built per hit: a
+    // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
+    {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
+    {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
 };
 // RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
 // move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)
 ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
     const char* force = getenv("RSPT_SHADE_VARIANT");
     if (move_out) *move_out = nullptr;
+    const bool sph = (need & SF_SPHERE) != 0;
     for (const ShadeVariant& v : g_shade_variants) {
+        if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
         if ((need & ~v.features) != 0) continue;
         if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;
         if (name_out) *name_out = v.name;
@@ -789,6 +805,7 @@ ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* 
         if (move_out && waves == (size_t)v.dflt) *move_out = v.move;
         return waves == 3 ? v.w3 : (waves == 4 ? v.w4 : v.natural);
     }
+    if (sph) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)
     return k_shade<SF_ALL>;
 }
 
@@ -799,8 +816,23 @@ constexpr int RSPT_DL_RETRY_LANE = -1000;   // batch_direct -> the batch loop: r
 int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, void* film_dev, float* li_host, rspt_stats* stats) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
-    // ABI 23: spheres are traced (rspt_trace) but not yet shaded, textured or sampled as lights on the device: the caller keeps its CPU loop
-    if (s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with spheres: rspt_render does not serve sphere shapes yet (rspt_trace does)");
+    // Analytic spheres are served as surfaces (hit, shaded, textured, blocking light) by the path and AO integrators in their wavefront form
+    // (Sobol' / Halton).  Everything else that holds a sphere is refused, so the caller keeps its CPU loop: sphere area lights (their
+    // sample_with_ref_point / pdf_with_ref_point and power are not on the device), the directlighting / whitted / volpath forms and the pixel
+    // samplers (their per-lane walks, trace_serial.h, have no sphere test), and a sphere scene whose records outgrow the four-box kernel.
+    if (s->has_spheres) {
+        static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
+        const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
+        if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: sphere area lights are not served on the device yet (%s)", iname);
+        if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+            return fail(RSPT_E_UNSUPPORTED, "scene with spheres under the %s integrator: spheres are served by path and ao only", iname);
+        if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+            return fail(RSPT_E_UNSUPPORTED, "scene with spheres under the %s sampler: spheres are served with the sobol and halton samplers only",
+                        d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                        d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+        if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "sphere scene with more four-box records than a reference holds");
+        if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with spheres: the sphere traversal keeps no node counters");
+    }
     // WhittedIntegrator::li runs on directlighting's machinery (direct.h / dl_serial.h, their WH forms) as UniformSampleAll with one estimate per light and
     // no sample arrays; max_depth 0 recurses no more than 1 does (whitted.rs:103: depth + 1 < max_depth)
     const bool whitted = d->integrator == RSPT_INTEGRATOR_WHITTED;
@@ -964,6 +996,8 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     LightDistDev ld;
     const LightDist* ld_lazy = nullptr;  // on-demand voxels: a mark / build round in front of every shade launch
     if ((rc = get_light_dist(s, d->light_strategy, &ld, &ld_lazy))) return rc;
+    // (k_ld_mark finds a hit's voxel from its barycentrics: a sphere scene takes the eager table or nothing)
+    if (ld_lazy && s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with spheres whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)");
     if (volpath && s->dev.n_grid_media && !pixel_sampler)
         return fail(RSPT_E_UNSUPPORTED, "volpath with a grid-density medium under the Sobol' / Halton sampler: every tracking step draws sampler dimensions (the reference panics past "
                                         "dimension 1024 / 1000 within a bounce or two); render it with a pixel sampler (random / 02sequence / stratified / maxmindist)");
@@ -1110,6 +1144,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     const char* shade_name = "generic";
     ShadeKernel shade_move_k = nullptr;
     const ShadeKernel shade_slot_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k);
+    if (!shade_slot_k) return fail(RSPT_E_UNSUPPORTED, "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
     const bool move = !volpath && !direct && !ao && !pixel_sampler && !s->has_animated && shade_move_k != nullptr && env_size("RSPT_MOVE", 1) != 0;
     // the first iteration that runs the MOVE kernel.  Iteration 0 reads a dense pixel-major queue whatever the schedule and its stores are dense too (every slot is
     // written): the slot-for-life kernel serves it (the MOVE form is 4 % slower there: 120 B of scratch against 36 at the same 168 VGPRs, profiles/r06_move_ab.txt),
@@ -1522,7 +1557,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
         launch_trace<false, 0>(0, counters, tgrid, s, g.q[0][1], &g.cnt[0].closest, 0, &g.cnt[0].cursor_closest, g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
         ev_close(0, 0);
         HIP_TRY(hipEventRecord(e1, g.stream));
-        hipLaunchKernelGGL(s->has_animated ? k_ao_spawn<true> : k_ao_spawn<false>, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, g.pix_list, ao_n, d->ao_cos_sample, g.q[0][2], &g.cnt[1]);
+        hipLaunchKernelGGL(s->has_spheres ? k_ao_spawn_sph : (s->has_animated ? k_ao_spawn<true> : k_ao_spawn<false>), dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, g.pix_list, ao_n, d->ao_cos_sample, g.q[0][2], &g.cnt[1]);
         HIP_TRY(hipEventRecord(e2, g.stream));
         ev_open(1, 0);
         s->dev.time_div = ao_n;   // shadow ray k of camera sample i sits in slot i * n + k: its Ray.time is the sample's (moving instances)
@@ -1593,7 +1628,7 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
             }
             if (s->has_textures) {
                 const bool tex_sorted = bins_now && env_size("RSPT_TEXTURE_SORTED", 1) != 0;
-                hipLaunchKernelGGL(k_texture, dim3(sgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, P, g.q[par][0], &g.cnt[it].active,
+                hipLaunchKernelGGL(s->has_spheres ? k_texture_sph : k_texture, dim3(sgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, P, g.q[par][0], &g.cnt[it].active,
                                    tex_sorted ? g.q_sorted : (const uint32_t*)nullptr, tex_sorted ? &g.bin_info[it] : (const BinInfo*)nullptr);
             }
             hipLaunchKernelGGL((move && it >= move_first) ? shade_move_k : shade_k, dim3(hinted_grid(sgrid, 256)), dim3(256), sob_nd * sob_bits * sizeof(uint32_t), g.stream, s->dev, ld, rd, P, g.q[par][0], &g.cnt[it], &g.cnt[it + 1], g.q[par ^ 1][0],
@@ -2729,6 +2764,9 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             e = hipMemcpy(tris + 3 * d->n_prims, sph.data(), sph.size() * sizeof(SphereDev), hipMemcpyHostToDevice);
             if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "sphere records: %s", hipGetErrorString(e)));
             s->has_spheres = true;
+            s->shade_features |= SF_SPHERE;
+            for (uint64_t i = 0; i < d->n_prims; i++)
+                if (d->prims[i].mesh == RSPT_MESH_SPHERE && d->prims[i].area_light != -1) s->has_sphere_light = true;
         }
         s->dev.tris = tris;
         if (s->w4_ok && s->w4 && !instanced && (!s->has_alpha || s->alpha_simple) && env_size("RSPT_SERIAL_W4", 1) != 0) {   // the per-lane kernels' traversal (trace_serial.h)
@@ -3019,7 +3057,8 @@ int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* ou
 int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3], float* func_out, float* cdf_out, int32_t nvox_out[3], int32_t voxel_out[3]) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
-    if (s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "sphere scenes: the light distributions are not built for sphere area lights yet");
+    // (a scene whose spheres are no lights needs no sphere code here: the spatial voxels take the world bound from the BVH root, which holds the spheres)
+    if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
     const uint32_t nl = s->dev.n_lights;
     if (nl == 0) return fail(RSPT_E_INVALID, "the scene has no lights");
     HIP_TRY(hipSetDevice(g.device));

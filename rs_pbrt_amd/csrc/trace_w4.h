@@ -134,7 +134,8 @@ RDEVN bool box_hit6_m(float lx, float ly, float lz, float hx, float hy, float hz
 #endif
 // SPH (ABI 23, scenes with spheres; never with INST): a leaf record carrying MF_SPHERE is a GeometricPrimitive over a Sphere — dev_sphere.h sphere_test
 // (Sphere::intersect / intersect_p up to t_shape_hit) on the world ray, reloaded from its queue record for the direction; its t becomes the ray's t_max
-// (primitive.rs:150-156).  b0..b2 of a sphere hit are 0.  The triangle instantiations (SPH = false) compile none of it.
+// (primitive.rs:150-156).  A sphere hit writes its primitive and its t: the hook's rspt_hit has t and b0..b2 = 0; the render's queue record
+// (OUT_MODE 0) is (prim, t, 0, 0), the shade stage recomputing the interaction (kernels.h sphere_fill).  The triangle instantiations (SPH = false) compile none of it.
 template <bool ANY, int OUT_MODE, bool INST, int ALPHA /* 0: no masks, 1: alpha_pass (any texture graph, a call), 2: alpha_simple (in line) */, bool ANIM = false,
           int BLOCK = RSPT_PW_BLOCK, int TOPCAP = RSPT_W4_TOP, bool SPH = false>
 __global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, TexTables tt, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, Te
                                 if (sphere_test(sp_rec->s, o, f3{r0.w, r1.x, r1.y}, t_max, &ts)) {
                                     if (ANY) { best = 0; break; }
                                     t_max = ts;      // primitive.rs:155
-                                    best = pi; bt = ts; bb0 = bb1 = bb2 = 0.0f;
+                                    best = pi; bt = ts; bb0 = OUT_MODE == 0 ? ts : 0.0f; bb1 = bb2 = 0.0f;   // (queue mode: the record's .y carries t)
                                 }
                                 continue;
                             }

@@ -19,6 +19,8 @@ constexpr uint32_t SV_GENERIC = SF_ALL & ~SF_DYNAMIC & ~SF_ANIM;
 // (212 VGPRs = 2 waves: C2 403 against Sobol's 473 M samples/s, the C3 stand-in 1705 against 2018)
 constexpr uint32_t SV_DIFFUSE_H = (SV_DIFFUSE & ~SF_SOBOL) | SF_HALTON, SV_PLASTIC_H = (SV_PLASTIC & ~SF_SOBOL) | SF_HALTON, SV_TEXTURED_H = (SV_TEXTURED & ~SF_SOBOL) | SF_HALTON;
 constexpr uint32_t SV_DYNAMIC = SF_ALL & ~SF_ANIM;                                                  // + per-hit lobe lists; SF_ALL itself: + moving instances
+// scenes with analytic spheres (dev_bsdf.h shade_sph): the generic and the dynamic set with the sphere arm; the sets above keep SF_TRIS_ONLY and so their code
+constexpr uint32_t SV_GENERIC_SPH = SV_GENERIC & ~SF_TRIS_ONLY, SV_DYNAMIC_SPH = SV_DYNAMIC & ~SF_TRIS_ONLY;
 
 #define RSPT_TU_TS(I, A, M) \
     RSPT_TU_X template __global__ void k_tile_serial<I, A, M>(SceneDev, TexTables, LightDistDev, RenderDev, PathBuf, PixDesc, const TileRec*, uint32_t, uint32_t, int32_t, int32_t, float4*, float2*, uint32_t, uint32_t*);
@@ -40,10 +42,11 @@ constexpr uint32_t SV_DYNAMIC = SF_ALL & ~SF_ANIM;                              
 #define RSPT_TU_W4B(ANY, OM, B, T) \
     RSPT_TU_X template __global__ void k_trace_w4<ANY, OM, false, 0, false, B, T>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, \
                                                                                    const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, uint32_t*, uint32_t*, uint32_t);   /* big workgroups, big LDS top */
-#define RSPT_TU_W4SPH(ANY, A) \
-    RSPT_TU_X template __global__ void k_trace_w4<ANY, 1, false, A, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, \
+#define RSPT_TU_W4SPH(ANY, A) RSPT_TU_W4SPHO(ANY, 1, A)
+#define RSPT_TU_W4SPHO(ANY, OM, A) \
+    RSPT_TU_X template __global__ void k_trace_w4<ANY, OM, false, A, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, \
                                                                   uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, \
-                                                                  uint32_t*, uint32_t*, uint32_t);   /* scenes with spheres (ABI 23): the trace hook */
+                                                                  uint32_t*, uint32_t*, uint32_t);   /* scenes with spheres: the trace hook (OM 1), the render's queues (OM 0) */
 #define RSPT_TU_W4_4(ANY, OM) RSPT_TU_W4(ANY, OM, false, 0) RSPT_TU_W4(ANY, OM, false, 1) RSPT_TU_W4(ANY, OM, true, 0) RSPT_TU_W4(ANY, OM, true, 1)
 #define RSPT_TU_W4_S(ANY, OM) RSPT_TU_W4(ANY, OM, false, 2) RSPT_TU_W4(ANY, OM, true, 2)   /* alpha masks evaluated in line (alpha_simple) */
 #define RSPT_TU_REF(ANY, OM, C, I, A) \
@@ -143,6 +146,9 @@ RSPT_TU_SHADE(SV_TEXTURED) RSPT_TU_SHADE_W(SV_TEXTURED, 3) RSPT_TU_SHADE_W(SV_TE
 RSPT_TU_SHADE(SV_GENERIC) RSPT_TU_SHADE_W(SV_GENERIC, 3) RSPT_TU_SHADE_W(SV_GENERIC, 4)
 RSPT_TU_SHADE(SV_DYNAMIC) RSPT_TU_SHADE(SF_ALL)
 #endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_S)
+RSPT_TU_SHADE(SV_GENERIC_SPH) RSPT_TU_SHADE(SV_DYNAMIC_SPH)   /* scenes with spheres; no MOVE form: they keep slots for life */
+#endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_H)
 RSPT_TU_SHADE(SV_DIFFUSE_H) RSPT_TU_SHADE_W(SV_DIFFUSE_H, 3) RSPT_TU_SHADE(SV_PLASTIC_H) RSPT_TU_SHADE_W(SV_PLASTIC_H, 3) RSPT_TU_SHADE(SV_TEXTURED_H) RSPT_TU_SHADE_W(SV_TEXTURED_H, 3)
 #endif
@@ -170,6 +176,9 @@ RSPT_TU_W4_S(false, 0) RSPT_TU_W4_S(false, 1) RSPT_TU_W4_S(true, 0) RSPT_TU_W4_S
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4SPH)
 RSPT_TU_W4SPH(false, 0) RSPT_TU_W4SPH(false, 1) RSPT_TU_W4SPH(false, 2) RSPT_TU_W4SPH(true, 0) RSPT_TU_W4SPH(true, 1) RSPT_TU_W4SPH(true, 2)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4SPH0)
+RSPT_TU_W4SPHO(false, 0, 0) RSPT_TU_W4SPHO(false, 0, 1) RSPT_TU_W4SPHO(false, 0, 2) RSPT_TU_W4SPHO(true, 0, 0) RSPT_TU_W4SPHO(true, 0, 1) RSPT_TU_W4SPHO(true, 0, 2)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4A)
 RSPT_TU_W4A(false, 0) RSPT_TU_W4A(false, 1) RSPT_TU_W4A(true, 0) RSPT_TU_W4A(true, 1)

@@ -3,7 +3,8 @@
 //! repo is built in); it is written against rs_pbrt v0.9.12 plus the getters of rust_shim/rs_pbrt.patch.  Everything not covered
 //! returns Err and `SamplerIntegrator::render` keeps its CPU tile loop (src/core/integrator.rs:70-220).
 //!
-//! Covered: triangle meshes (Shape::Trngl) under a BVHAccel aggregate, object instances (Primitive::Transformed, static or moving),
+//! Covered: triangle meshes (Shape::Trngl) and spheres (Shape::Sphr; not next to object instances, and a frame with an emissive sphere, or one
+//! rendered by another integrator than path / ao or with a pixel sampler, comes back Err from rspt_render) under a BVHAccel aggregate, object instances (Primitive::Transformed, static or moving),
 //! matte / plastic / mirror / glass (smooth and rough) / metal / substrate / uber / translucent / mix (handed over as their
 //! parameters — one texture reference each, rspt_material_desc; the library assembles the lobes), diffuse area / point / spot / distant / infinite lights (the light's own MIP
 //! pyramid and Distribution2D image are handed over), homogeneous media, PerspectiveCamera, the Sobol', Halton and the four
@@ -57,7 +58,7 @@ type FloatTex = Arc<dyn Texture<Float> + Sync + Send>;
 /// Everything that has to stay alive until rspt_scene_create has copied it.
 #[derive(Default)]
 struct Flat {
-    nodes: Vec<RsptBvhNode>, prims: Vec<RsptPrim>, meshes: Vec<RsptMesh>,
+    nodes: Vec<RsptBvhNode>, prims: Vec<RsptPrim>, meshes: Vec<RsptMesh>, spheres: Vec<RsptSphere>,   // spheres: ABI 23
     p: Vec<f32>, n: Vec<f32>, s: Vec<f32>, uv: Vec<f32>, any_n: bool, any_s: bool, any_uv: bool,
     materials: Vec<RsptMaterialDesc>, lights: Vec<RsptLight>,
     objects: Vec<RsptObject>, instances: Vec<RsptInstance>,
@@ -219,8 +220,26 @@ impl Flat {
         let mut pending: Vec<(usize, Arc<Primitive>, Transform)> = Vec::new();     // instances: flattened after this aggregate
         for prim in &bvh.primitives {                                              // BVH leaf order (bvh.rs:144-149)
             match &**prim {
+                Primitive::Geometric(g) if matches!(&*g.shape, Shape::Sphr(_)) => {
+                    // a GeometricPrimitive over a Sphere (ABI 23): what Sphere holds (sphere.rs:21-35) -> rspt_sphere, the primitive -> an rspt_prim with
+                    // mesh = RSPT_MESH_SPHERE and v[0] = the sphere's index.  An emissive sphere names its DiffuseAreaLight and light_record names the
+                    // primitive back (the pairing the library checks); rspt_render refuses sphere lights, so such a frame stays on the CPU loop.
+                    let sph = match &*g.shape { Shape::Sphr(x) => x, _ => unreachable!() };
+                    if !top { return Err("sphere inside an object instance".into()); }   // (the library refuses spheres next to instances)
+                    let (medium_inside, medium_outside) = match &g.medium_interface { Some(i) => (self.medium(&i.inside)?, self.medium(&i.outside)?), None => (0, 0) };
+                    let area_light = match &g.area_light {
+                        Some(al) => lights.iter().position(|l| Arc::ptr_eq(l, al)).map(|i| i as i32).unwrap_or(-1),
+                        None => -1,
+                    };
+                    let material = self.material(&g.material)?;
+                    self.spheres.push(RsptSphere { object_to_world: m16(&sph.object_to_world.m), world_to_object: m16(&sph.world_to_object.m),
+                                                   radius: sph.radius, z_min: sph.z_min, z_max: sph.z_max, theta_min: sph.theta_min, theta_max: sph.theta_max,
+                                                   phi_max: sph.phi_max, reverse_orientation: sph.reverse_orientation as u32,
+                                                   transform_swaps_handedness: sph.transform_swaps_handedness as u32, medium_inside, medium_outside });
+                    self.prims.push(RsptPrim { v: [(self.spheres.len() - 1) as u32, 0, 0], mesh: RSPT_MESH_SPHERE, material, area_light });
+                }
                 Primitive::Geometric(g) => {
-                    let tri = match &*g.shape { Shape::Trngl(t) => t, _ => return Err("non-triangle shape".into()) };
+                    let tri = match &*g.shape { Shape::Trngl(t) => t, _ => return Err("shape other than triangles and spheres".into()) };
                     let (mesh, first) = self.mesh(tri.mesh(), &g.medium_interface)?; // Triangle.mesh getter: rs_pbrt.patch (triangle.rs:85)
                     let vi = &tri.mesh().vertex_indices[3 * tri.id as usize..3 * tri.id as usize + 3];
                     let area_light = match &g.area_light {                         // the reference compares these pointers (integrator.rs:540-543)
@@ -391,6 +410,7 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         objects: f.objects.as_ptr(), n_objects: f.objects.len() as u32, instances: f.instances.as_ptr(), n_instances: f.instances.len() as u32,
         n_top_nodes, n_top_prims, instancing_mode: (std::env::var_os("RSPT_INSTANCING_FIXED").is_some()) as u32,
         n_media: f.media.len() as u32, media: if f.media.is_empty() { std::ptr::null() } else { f.media.as_ptr() },
+        spheres: if f.spheres.is_empty() { std::ptr::null() } else { f.spheres.as_ptr() }, n_spheres: f.spheres.len() as u32, pad_spheres: 0,
     };
     unsafe {
         if rspt_abi_version() != RSPT_ABI_VERSION { return Err("librspt.so ABI version mismatch".into()); }

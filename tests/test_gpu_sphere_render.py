@@ -1,0 +1,290 @@
+"""-m gpu: analytic spheres as surfaces in rspt_render — the path and AO integrators under Sobol' and Halton.  Every camera sample's radiance
+equals a hand restatement of PathIntegrator::li / AOIntegrator::li over a scene view that intersects spheres (tests/sphere_render_restated.cpp,
+held to the oracle's own li on triangle scenes by tests/test_sphere_render_host.py) bit for bit; a sphere no ray reaches changes nothing; a
+sphere casts its analytic shadow; a furnace sphere returns its albedo; and what stays out of scope is refused."""
+import math
+
+import numpy as np
+import pytest
+
+from rs_pbrt_amd import abi, scenes
+from tests.test_sphere_render_host import assert_same_li, build_restated, restated_render
+from tests.util import film_rmse, texture_image
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+LOOK = ((0, 2.2, -6.5), (0, 1.0, 0), (0, 1, 0))
+
+
+def rot(axis, deg):
+    a = math.radians(deg)
+    c, s = math.cos(a), math.sin(a)
+    x, y, z = np.asarray(axis, float) / np.linalg.norm(axis)
+    m = np.eye(4)
+    m[:3, :3] = [[c + x * x * (1 - c), x * y * (1 - c) - z * s, x * z * (1 - c) + y * s],
+                 [y * x * (1 - c) + z * s, c + y * y * (1 - c), y * z * (1 - c) - x * s],
+                 [z * x * (1 - c) - y * s, z * y * (1 - c) + x * s, c + z * z * (1 - c)]]
+    return m
+
+
+def xf(t, axis=(0, 1, 0), deg=0.0, scale=(1, 1, 1)):
+    m = rot(axis, deg)
+    m[:3, :3] = m[:3, :3] @ np.diag(scale)
+    m[:3, 3] = t
+    return scenes.Transform(m.astype(F32))
+
+
+def sphere_gallery(builder, lights="all", camera_inside=False):
+    """floor + back wall, an alpha-masked panel, and spheres of every material recipe: full, z- and phi-clipped, mirrored and non-uniformly
+    scaled, glass (refraction through a sphere), a null-material sphere, textured spheres (UV and spherical mapping, bump)"""
+    sb = scenes.SceneBuilder()
+    img = texture_image()
+    floor = sb.add_material(scenes.matte((0.5, 0.5, 0.5)))
+    wall = sb.add_material(scenes.matte(sb.image_texture(img, su=2.0, sv=2.0)))
+    sb.add_quad([(-6, 0, -6), (6, 0, -6), (6, 0, 6), (-6, 0, 6)], floor)
+    sb.add_quad([(-6, 0, 4), (6, 0, 4), (6, 6, 4), (-6, 6, 4)], wall, UV=[[0, 0], [1, 0], [1, 1], [0, 1]])
+    cut = sb.checkerboard_texture(sb.constant_texture(0.0), sb.constant_texture(1.0), su=4.0, sv=4.0)
+    sb.add_quad([(2.2, 0.1, -1.2), (3.6, 0.1, -0.6), (3.6, 2.0, -0.6), (2.2, 2.0, -1.2)], sb.add_material(scenes.matte((0.2, 0.6, 0.3))),
+                UV=[[0, 0], [1, 0], [1, 1], [0, 1]], alpha=cut)
+    height = sb.image_texture(img, channels=1, scale=0.05, trilinear=True)
+    mats = [scenes.matte((0.7, 0.3, 0.2), sigma=20.0), scenes.plastic((0.2, 0.3, 0.6), (0.4, 0.4, 0.4), 0.1),
+            scenes.glass((1.0, 1.0, 1.0), (1.0, 1.0, 1.0), 1.5), scenes.metal(roughness=0.05), scenes.mirror((0.9, 0.9, 0.9)),
+            scenes.substrate((0.5, 0.4, 0.3), (0.2, 0.2, 0.2), 0.1, 0.2), scenes.uber((0.3, 0.5, 0.3), (0.2, 0.2, 0.2), (0.1, 0.1, 0.1), (0.0, 0.0, 0.0), 0.2),
+            scenes.translucent((0.4, 0.4, 0.2), (0.2, 0.2, 0.2), (0.5, 0.5, 0.5), (0.4, 0.4, 0.4), 0.2), scenes.rough_glass(uroughness=0.1, vroughness=0.2),
+            scenes.mix(scenes.matte((0.8, 0.2, 0.2)), scenes.plastic((0.1, 0.1, 0.8), (0.3, 0.3, 0.3), 0.1), (0.4, 0.5, 0.6)),
+            scenes.matte(sb.image_texture(img, su=3.0, sv=2.0), bump=height),
+            scenes.plastic(sb.image_texture(img, mapping="spherical"), (0.3, 0.3, 0.3), 0.15, bump=height)]
+    ids = [sb.add_material(m) for m in mats]
+    k = 0
+    for row in range(3):
+        for col in range(4):
+            c = (-3.3 + 2.2 * col, 0.55 + 0.05 * row, -2.0 + 1.9 * row)
+            r = 0.5
+            kind = k % 4
+            if kind == 0:
+                sb.add_sphere(r, object_to_world=xf(c), material=ids[k])
+            elif kind == 1:
+                sb.add_sphere(r, zmin=-0.3, zmax=0.35, object_to_world=xf(c, (1, 0, 0), 70), material=ids[k])
+            elif kind == 2:
+                sb.add_sphere(r, phimax=250.0, object_to_world=xf(c, (0.3, 1, 0.2), 40), material=ids[k])
+            else:   # mirrored, non-uniformly scaled
+                sb.add_sphere(r, object_to_world=xf(c, (0, 0, 1), 25, scale=(-1.2, 0.8, 1.0)), material=ids[k])
+            k += 1
+    sb.add_sphere(0.45, object_to_world=xf((0.6, 2.6, 0.5)), material=None)   # a null-material sphere: rays pass through it
+    if lights in ("all", "area"):
+        sb.add_quad([(-1, 5.0, -1), (1, 5.0, -1), (1, 5.0, 1), (-1, 5.0, 1)], floor, emit=(9, 9, 9))
+    if lights in ("all", "delta"):
+        sb.add_point_light((2.5, 3.5, -2.5), (6, 6, 6))
+        sb.add_spot_light((-3, 4, -3), (0, 0.5, 0), (20, 18, 16), 30.0, 5.0)
+        sb.add_distant_light((1, 3, -2), (0, 0, 0), (0.6, 0.6, 0.6))
+    if lights in ("all", "sky"):
+        sb.add_infinite_light((0.3, 0.35, 0.45))
+    if camera_inside:   # a big sphere around the camera: its inside is seen, and light comes in through its clipped-away cap
+        sb.add_sphere(3.0, zmin=-3.0, zmax=2.2, object_to_world=xf((0, 2.2, -6.5), (1, 0, 0), -90), material=ids[0])
+    return sb.finish(builder)
+
+
+@pytest.fixture(scope="module")
+def restated():
+    return build_restated()
+
+
+def parity(gpu, restated, sc, rd, rmse=1e-5):
+    with gpu.DeviceScene(sc) as ds:
+        li, _ = gpu.render_samples(ds, rd)
+        film, _ = gpu.render(ds, rd)
+    want_film, want = restated_render(restated, sc, rd)
+    assert_same_li(li, want)
+    assert film_rmse(film, want_film) < rmse
+    return li
+
+
+CASES = [("all", "sobol", "path", abi.LIGHTS_SPATIAL, 7), ("all", "halton", "path", abi.LIGHTS_POWER, 5), ("delta", "sobol", "path", abi.LIGHTS_UNIFORM, 3),
+         ("area", "halton", "path", abi.LIGHTS_SPATIAL, 9), ("sky", "sobol", "path", abi.LIGHTS_POWER, 6),
+         ("all", "sobol", "ao", abi.LIGHTS_SPATIAL, 5), ("all", "halton", "ao", abi.LIGHTS_SPATIAL, 5)]
+
+
+@pytest.mark.parametrize("lights,sampler,integrator,strategy,depth", CASES)
+def test_sphere_gallery_li_equals_restated_li(gpu, restated, lights, sampler, integrator, strategy, depth):
+    sc = sphere_gallery(gpu.bvh_build, lights)
+    assert (sc.prims["mesh"] == abi.MESH_SPHERE).sum() == 13
+    rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=depth, sampler=sampler, integrator=integrator, light_strategy=strategy, ao_samples=4)
+    li = parity(gpu, restated, sc, rd)
+    assert np.nanmean(li) > 0.0
+
+
+def test_camera_inside_a_sphere(gpu, restated):
+    sc = sphere_gallery(gpu.bvh_build, "all", camera_inside=True)
+    rd = scenes.make_render_desc(40, 30, 4, LOOK, 70, max_depth=5)
+    parity(gpu, restated, sc, rd)
+
+
+@pytest.mark.parametrize("streams", ["1", None])
+def test_batches_and_trace_streams(gpu, restated, monkeypatch, streams):
+    """a batch too small for the frame (several batches), with the shadow-ray launch on its own stream (default) or not"""
+    sc = sphere_gallery(gpu.bvh_build, "all")
+    rd = scenes.make_render_desc(40, 30, 8, LOOK, 60, max_depth=6)
+    monkeypatch.setenv("RSPT_BATCH", str(1 << 11))
+    if streams:
+        monkeypatch.setenv("RSPT_TRACE_STREAMS", streams)
+    parity(gpu, restated, sc, rd)
+
+
+def _closed_box_scene(builder, with_sphere):
+    sb = scenes.SceneBuilder()
+    g = sb.add_material(scenes.matte((0.6, 0.6, 0.6)))
+    p = sb.add_material(scenes.plastic((0.3, 0.2, 0.5), (0.3, 0.3, 0.3), 0.1))
+    sb.add_quad([(-6, 0, -6), (6, 0, -6), (6, 0, 6), (-6, 0, 6)], g)
+    sb.add_box((-1.0, 0.0, -1.0), (1.0, 2.0, 1.0), p)   # closed and opaque: nothing reaches inside
+    sb.add_quad([(-1, 5.0, -1), (1, 5.0, -1), (1, 5.0, 1), (-1, 5.0, 1)], g, emit=(9, 9, 9))
+    sb.add_point_light((2.5, 3.5, -2.5), (6, 6, 6))
+    if with_sphere:
+        sb.add_sphere(0.6, object_to_world=xf((0, 1, 0)), material=g)
+    return sb.finish(builder)
+
+
+@pytest.mark.parametrize("sampler", ["sobol", "halton"])
+def test_a_sphere_no_ray_reaches_changes_nothing(gpu, sampler):
+    """a sphere inside a closed opaque box: every sample equals the same scene's without it, bit for bit — the sphere variant of the shade
+    stage (and the sphere traversal) treat triangles exactly as the triangle variants do.  The scene without the sphere keeps the very same
+    tree: the sphere's primitive becomes a degenerate triangle, which no ray can hit."""
+    rd = scenes.make_render_desc(48, 36, 8, LOOK, 60, max_depth=6, sampler=sampler)
+    with_sphere = _closed_box_scene(gpu.bvh_build, True)
+    without = _closed_box_scene(gpu.bvh_build, True)
+    k = int(np.nonzero(without.prims["mesh"] == abi.MESH_SPHERE)[0][0])
+    without.prims["mesh"][k] = 0
+    without.prims["v"][k] = 0
+    without.desc.n_spheres = 0
+    out = []
+    for sc in (without, with_sphere):
+        with gpu.DeviceScene(sc) as ds:
+            out.append(gpu.render_samples(ds, rd)[0])
+    assert out[0].mean() > 0.01
+    assert np.array_equal(out[0].view(np.uint32), out[1].view(np.uint32))
+
+
+def test_analytic_shadow_of_a_sphere(gpu):
+    """path, max_depth 1, a matte plane lit by a point light straight above a grey sphere, seen from straight above: every pixel whose shading
+    point lies well inside the sphere's shadow cone but well outside the part of the plane the sphere hides from the camera gets exactly 0
+    direct light; pixels well outside the cone equal the sphere-free render bit for bit.  The sphere sits high and small, so the cone's
+    unobstructed ring is several pixels wide."""
+    h, R, cy, H = 6.0, 0.5, 4.0, 12.0
+
+    def scene(with_sphere):
+        sb = scenes.SceneBuilder()
+        g = sb.add_material(scenes.matte((0.5, 0.5, 0.5)))
+        sb.add_quad([(-8, 0, -8), (8, 0, -8), (8, 0, 8), (-8, 0, 8)], g)
+        sb.add_point_light((0.0, h, 0.0), (40, 40, 40))
+        if with_sphere:
+            sb.add_sphere(R, object_to_world=xf((0.0, cy, 0.0)), material=g)
+        return sb.finish(gpu.bvh_build)
+
+    rd = scenes.make_render_desc(96, 96, 1, ((0, H, 0), (0, 0, 0), (0, 0, 1)), 50, max_depth=1, sample_at_pixel_center=True)
+    free, occ = [], []
+    for with_sphere, out in ((False, free), (True, occ)):
+        with gpu.DeviceScene(scene(with_sphere)) as ds:
+            out.append(gpu.render_samples(ds, rd)[0][:, 0, :])
+    free, occ = free[0], occ[0]
+    y = free.astype(np.float64).sum(-1)
+    assert y.min() > 0
+    # a point light over a Lambertian plane: radiance ~ h / r^3, so the horizontal distance of a pixel's shading point from the light's foot
+    # follows from its radiance relative to the brightest pixel (whose point lies within half a pixel of the foot); the camera stands over
+    # the same foot, so the same distance places the pixel's view ray
+    rho = np.sqrt(np.maximum(h * h * ((y.max() / y) ** (2.0 / 3.0) - 1.0), 0.0))
+    rho_shadow = h * R / math.sqrt((h - cy) ** 2 - R * R)   # the cone from the light tangent to the sphere meets the plane in a disk of this radius
+    rho_hidden = H * R / math.sqrt((H - cy) ** 2 - R * R)   # ... and the cone from the camera: the plane the sphere hides from view
+    ring = (rho > 1.2 * rho_hidden) & (rho < 0.85 * rho_shadow)
+    outer = rho > 1.15 * rho_shadow
+    assert ring.sum() > 150 and outer.sum() > 3000
+    assert np.all(occ[ring] == 0.0) and np.all(free[ring] > 0.0)
+    assert np.array_equal(occ[outer].view(np.uint32), free[outer].view(np.uint32))
+    assert np.all(occ[rho < 0.8 * rho_hidden].sum(-1) > 0.0)   # the sphere's lit top, seen from above
+
+
+def test_sphere_scene_with_an_on_demand_light_table_refused(gpu, monkeypatch):
+    """a spatial light table larger than RSPT_LIGHT_TABLE_EAGER_BYTES is built voxel by voxel as paths find them, and that search starts from
+    triangle barycentrics: a sphere scene then keeps its CPU loop"""
+    sc = sphere_gallery(gpu.bvh_build, "all")
+    rd = scenes.make_render_desc(16, 16, 4, LOOK, 60, light_strategy=abi.LIGHTS_SPATIAL)
+    monkeypatch.setenv("RSPT_LIGHT_TABLE_EAGER_BYTES", "0")
+    with gpu.DeviceScene(sc) as ds:
+        with pytest.raises(gpu.RsptError) as e:
+            gpu.render(ds, rd)
+        assert e.value.code == abi.E_UNSUPPORTED and "sphere" in str(e.value) and "on-demand" in str(e.value)
+    monkeypatch.delenv("RSPT_LIGHT_TABLE_EAGER_BYTES")
+    with gpu.DeviceScene(sc) as ds:
+        film, _ = gpu.render(ds, rd)
+    assert film[:, 3].sum() > 0
+
+
+def test_furnace_sphere(gpu):
+    """a matte sphere of Kd = 0.5 under a constant infinite light of radiance 1, nothing else: every path that meets the sphere returns 0.5
+    in expectation; the mean over the sphere's camera samples is 0.5 within five standard errors of those samples"""
+    sb = scenes.SceneBuilder()
+    sb.add_sphere(1.0, object_to_world=xf((0, 0, 0)), material=sb.add_material(scenes.matte((0.5, 0.5, 0.5))))
+    sb.add_infinite_light((1.0, 1.0, 1.0))
+    sb.add_mesh(np.array([(0, -1000, 0), (0.01, -1000, 0), (0, -1000, 0.01)], F32), [[0, 1, 2]], sb.add_material(scenes.matte((0.5, 0.5, 0.5))))   # (a scene holds a mesh: 1e-10 sr)
+    sc = sb.finish(gpu.bvh_build)
+    rd = scenes.make_render_desc(32, 32, 64, ((0, 0, -4), (0, 0, 0), (0, 1, 0)), 40, max_depth=50, light_strategy=abi.LIGHTS_SPATIAL)
+    with gpu.DeviceScene(sc) as ds:
+        li = gpu.render_samples(ds, rd)[0]
+    y = li.mean(-1)
+    on = np.all(np.abs(y - 1.0) > 1e-6, axis=1)   # pixels whose every sample met the sphere (escaped camera rays return exactly 1)
+    assert on.sum() > 200
+    s = y[on].ravel().astype(np.float64)
+    se = s.std(ddof=1) / math.sqrt(len(s))
+    assert abs(s.mean() - 0.5) < 5 * se + 1e-4, (s.mean(), se)
+
+
+def _plain_sphere_room(gpu, emit=None):
+    sb = scenes.SceneBuilder()
+    mat = sb.add_material(scenes.matte((0.5, 0.5, 0.5)))
+    sb.add_quad([(-5, 0, -5), (5, 0, -5), (5, 0, 5), (-5, 0, 5)], mat)
+    sb.add_quad([(-1, 4, -1), (1, 4, -1), (1, 4, 1), (-1, 4, 1)], mat, emit=(5, 5, 5))
+    sb.add_point_light((2, 3, -2), (4, 4, 4))
+    sb.add_sphere(1.0, object_to_world=xf((0, 1, 0)), material=mat, emit=emit)
+    return sb.finish(gpu.bvh_build)
+
+
+@pytest.mark.parametrize("integrator", ["path", "ao", "directlighting", "whitted", "volpath"])
+def test_emissive_sphere_refused_everywhere(gpu, integrator):
+    sc = _plain_sphere_room(gpu, emit=(1.0, 1.0, 1.0))
+    rd = scenes.make_render_desc(16, 16, 4, LOOK, 45.0, integrator=integrator)
+    with gpu.DeviceScene(sc) as ds:
+        with pytest.raises(gpu.RsptError) as e:
+            gpu.render(ds, rd)
+        assert e.value.code == abi.E_UNSUPPORTED and "sphere area light" in str(e.value)
+        for strategy in (abi.LIGHTS_POWER, abi.LIGHTS_SPATIAL, abi.LIGHTS_UNIFORM):
+            with pytest.raises(gpu.RsptError) as e:
+                gpu.light_distribution(ds, strategy, (0.0, 0.5, 0.0))
+            assert e.value.code == abi.E_UNSUPPORTED and "sphere" in str(e.value)
+
+
+@pytest.mark.parametrize("integrator,sampler,word", [("directlighting", "sobol", "directlighting"), ("whitted", "halton", "whitted"), ("volpath", "sobol", "volpath"),
+                                                     ("path", "random", "random"), ("path", "02sequence", "02sequence"), ("ao", "stratified", "stratified"),
+                                                     ("path", "maxmindist", "maxmindist")])
+def test_out_of_scope_sphere_renders_refused(gpu, integrator, sampler, word):
+    sc = _plain_sphere_room(gpu)
+    rd = scenes.make_render_desc(16, 16, 16, LOOK, 45.0, integrator=integrator, sampler=sampler, strat=(4, 4))
+    with gpu.DeviceScene(sc) as ds:
+        with pytest.raises(gpu.RsptError) as e:
+            gpu.render(ds, rd)
+        assert e.value.code == abi.E_UNSUPPORTED and "sphere" in str(e.value) and word in str(e.value)
+
+
+def test_light_distribution_served_on_a_sphere_scene(gpu, oracle):
+    """no sphere is a light: the hook serves the scene, and its voxel tables equal the oracle's (the world bound is the BVH root's, spheres included)"""
+    import ctypes as C
+    sc = sphere_gallery(gpu.bvh_build, "all")
+    rd = scenes.make_render_desc(32, 24, 1, LOOK, 60)
+    nl = int(sc.desc.n_lights)
+    lo, hi = sc.nodes["bmin"][0], sc.nodes["bmax"][0]
+    pts = np.random.default_rng(4).uniform(lo - 0.5, hi + 0.5, (40, 3)).astype(F32)
+    with gpu.DeviceScene(sc) as ds:
+        for p in pts:
+            f, c, nv, vx = gpu.light_distribution(ds, abi.LIGHTS_SPATIAL, p)
+            of, oc, onv = np.zeros(nl, F32), np.zeros(nl + 1, F32), (C.c_int32 * 3)()
+            oracle.lib().orc_spatial_voxel(C.addressof(sc.desc), C.addressof(rd), (C.c_int32 * 3)(*map(int, vx)), of.ctypes.data, oc.ctypes.data, onv)
+            assert list(nv) == list(onv) and np.array_equal(f, of) and np.array_equal(c, oc)
+        f, c, _, _ = gpu.light_distribution(ds, abi.LIGHTS_POWER, pts[0])
+        assert f.min() > 0 and c[0] == 0 and abs(c[-1] - 1) < 1e-6
