@@ -1,0 +1,237 @@
+// One launch of the traversal stage: the descriptor a caller fills (TraceCall), the kernel choice per scene and switch, and the shade stage's
+// instantiations.  Host code of librspt.hip, included there once inside its anonymous namespace (it uses that file's Ctx g and allocators).
+// upper bound of the queue lengths of the launches that follow, when the host knows one (the null-surface tail of a render looks at
+// its queue every 8th iteration and the queues only shrink): a few hundred paths do not need 1280 persistent workgroups each copying
+// the root-side records into LDS
+uint32_t hinted_grid(uint32_t hint, uint32_t full, uint32_t per_block) {
+    if (hint == 0xffffffffu) return full;
+    const uint64_t need = (2ull * hint + per_block - 1) / per_block + 1;
+    return (uint32_t)std::min<uint64_t>(full, need);
+}
+// does the production trace kernel ever hand rays to k_trace_fixup?  Not the four-box kernel with all its spill rows (RSPT_W4_MAX_STACK)
+bool trace_can_overflow(const rspt_scene_s* s) {
+    const size_t which = env_size("RSPT_TRACE_KERNEL", 2);
+    const size_t rows = std::min<size_t>(env_size("RSPT_W4_SPILL_ROWS", RSPT_W4_SPILL), RSPT_W4_SPILL);
+    return s->has_instances || (s->has_alpha && !s->w4_ok) || !(which >= 2 && s->w4_ok) || RSPT_W4_LDS + rows < RSPT_W4_MAX_STACK;  // (two stacked aggregates + leaf continuations can pass the bound)
+}
+uint32_t trace_grid() { return grid_for((uint32_t)env_size("RSPT_TRACE_BLOCKS_PER_CU", 5)); }
+// One launch of the traversal stage.  Kernel choice: scenes with object instances or alpha-masked meshes take the <INST, ALPHA>
+// instantiations (template flags, so that the plain kernels stay the ones measured in DESIGN.md); counters and RSPT_TRACE_KERNEL=0
+// use the reference-order loop; a scene whose records outgrow the four-box reference fields stays on the two-box kernel.
+#ifndef RSPT_PW_CHUNK_CAMERA_DEFAULT
+#define RSPT_PW_CHUNK_CAMERA_DEFAULT 1024   // measured on the C3 stand-in, same box, alternating: 256 -> 2025 / 2029, 1024 -> 2075 / 2070, 4096 -> 2024 / 2030, 16384 -> 1900 Msamples/s
+                                            // (C2: 473.9 / 473.3 / 471.1 at 256 / 1024 / 4096); the incoherent launches keep 256 (512: C3 2061 with the camera launch at 1024)
+#endif
+#ifndef RSPT_PW_REFILL_CAMERA_DEFAULT
+#define RSPT_PW_REFILL_CAMERA_DEFAULT 48   // a wave of coherent camera rays refills when three quarters of its lanes are idle (the incoherent launches: RSPT_PW_REFILL = 16)
+#endif
+#ifndef RSPT_PW_ENTER
+#define RSPT_PW_ENTER 24   // C5 stand-in, every instance moving (profiles/r06_c5_enter_sweep.txt): 1 -> 142, 8 -> 170, 16 -> 182, 24 -> 183, 32 -> 180 Msamples/s
+#endif
+// What one trace launch reads and writes.  Every field defaults to "absent": a call site names what it uses.
+struct TraceCall {
+    const uint32_t* queue = nullptr; const uint32_t* count_ptr = nullptr; uint32_t count_imm = 0;   // the queue entries to trace; their number on the device, or known to the host
+    uint32_t* cursor = nullptr;                                  // the persistent kernels' fetch cursor (QueueCounts: the overflow word sits two after it)
+    const rspt_ray* ra = nullptr; const rspt_ray* rb = nullptr;  // rays / outputs of the entries without / with the MIS flag
+    float4* oa = nullptr; float4* ob = nullptr;
+    uint32_t* occ = nullptr;                                     // any hit: the occlusion flags
+    rspt_hit* hits = nullptr;                                    // OUT_MODE 1 (the trace hook): full hit records
+    unsigned long long* counters = nullptr; uint32_t* xcd_cursors = nullptr;   // the node / triangle counters; eight zeroed words: XCD-affine dealing where RSPT_XCD_DEAL asks for it
+    int lane = 0;                      // 0 = the library's main stream; 1 = the second stream with its own overflow list and spill rows
+    bool count = false;                // the reference-order kernel with its node / triangle counters
+    bool camera_launch = false;        // the camera rays of a batch (a pixel-major queue): RSPT_PW_CHUNK_CAMERA / _REFILL_CAMERA / _LEAF_CAMERA
+    int force_any_q = -1;              // tune_any's measurement of the two shadow-ray kernels: 0 / 1 forces the plain / the quantised one
+    uint32_t* inst_out = nullptr;      // where a closest-hit launch records the instance of each hit instead of g.hit_inst (volpath's shadow-ray segments)
+    uint32_t queue_hint = 0xffffffffu; // upper bound of the queue's length when the host knows one (hinted_grid), 0xffffffff: none
+};
+// what every persistent-wave launch needs besides its kernel: the lane's stream with its overflow list and spill rows, the hinted grid, the refill / leaf-phase
+// thresholds and the claim size.  `camera`: the camera-ray launch's own values; the sphere kernels never take them
+struct TracePre { hipStream_t stream; uint32_t* ovf; uint2* spill; uint32_t pgrid; int refill, leaf; uint32_t chunk; };
+TracePre trace_pre(const TraceCall& c, bool camera) {
+    TracePre p; p.stream = c.lane ? g.stream2 : g.stream;
+    p.ovf = g.ovf + (c.lane ? 2 * g.ovf_cap / 3 : 0);
+    p.spill = g.spill + (c.lane ? g.spill_threads * RSPT_W4_SPILL : 0);
+    p.pgrid = hinted_grid(c.queue_hint, pw_grid(), RSPT_PW_BLOCK);
+    // rays a wave claims per global atomic: 256 for the incoherent launches; the camera-ray launch of a batch (pixel-major queue: a chunk is a run of samples of one pixel
+    // or its neighbours) takes RSPT_PW_CHUNK_CAMERA (TraceCall::camera_launch, set by the path integrator's loop)
+    // refill / leaf-phase thresholds; the camera-ray launch may take its own (RSPT_PW_REFILL_CAMERA / RSPT_PW_LEAF_CAMERA: coherent rays reach their leaves together)
+    // (camera launch, C3 stand-in, one box, alternating: refill 16 -> 2079 / 2067 Msamples/s, 32 -> 2083 / 2083, 48 -> 2114 / 2113, 64 -> 2105 / 2101; leaf 16 / 24 / 32 at refill 16: 2061 / 2059 / 2046)
+    p.refill = (int)(camera ? env_size("RSPT_PW_REFILL_CAMERA", RSPT_PW_REFILL_CAMERA_DEFAULT) : env_size("RSPT_PW_REFILL", RSPT_PW_REFILL));
+    p.leaf = (int)(camera ? env_size("RSPT_PW_LEAF_CAMERA", env_size("RSPT_PW_LEAF", RSPT_PW_LEAF)) : env_size("RSPT_PW_LEAF", RSPT_PW_LEAF));
+    p.chunk = (uint32_t)std::min<size_t>(std::max<size_t>((camera ? env_size("RSPT_PW_CHUNK_CAMERA", RSPT_PW_CHUNK_CAMERA_DEFAULT) : env_size("RSPT_PW_CHUNK", RSPT_PW_CHUNK)) & ~(size_t)63, 64), 1u << 20);
+    return p;
+}
+template <bool ANY, int OUT_MODE, bool INST, bool ALPHA>
+void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur) {
+    const SceneDev& sc = s->dev;
+    // RSPT_TRACE_KERNEL: 0 = k_trace (reference-order single-ray loop), 1 = k_trace_pw (persistent waves, two boxes
+    // per record), 2 = k_trace_w4 (persistent waves, four boxes per record; default).
+    // (A quad-per-ray variant with one coalesced 64-byte fetch per step was measured 35 % slower: the
+    //  replicated control flow made it VALU-bound with 16 rays per wave)
+    const size_t which = env_size("RSPT_TRACE_KERNEL", 2);
+    const TracePre p = trace_pre(c, c.camera_launch);
+    uint32_t* hi = (INST && OUT_MODE == 0 && !ANY) ? (c.inst_out ? c.inst_out : g.hit_inst) : nullptr;
+    const bool special = INST || ALPHA;
+    // moving instances: k_trace_w4<.., INST, 0, ANIM> (round 5; RSPT_ANIM_W4=0: the reference-order loop with the interpolation, as before)
+    const bool anim_w4 = s->has_animated && s->w4_ok && which >= 2 && env_size("RSPT_ANIM_W4", 1) != 0 && env_size("RSPT_INSTANCE_KERNEL", 1) != 0;   // (round 6: the reference-order loop serves moving instances next to masks too, so every A/B switch stays bit-exact)
+    const bool slow = c.count || which == 0 || (s->has_animated && !anim_w4) || (special && (!s->w4_ok || env_size("RSPT_INSTANCE_KERNEL", 1) == 0));
+    if (slow) {
+        if (INST && s->has_animated)   // moving instances (alone or next to alpha-masked meshes): the reference-order loop with the interpolation (its own instantiations; no node / triangle counters)
+            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+        else if (c.count)
+            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, true, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+        else
+            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+        return;
+    }
+    const uint32_t pw_chunk = p.chunk | (env_size("RSPT_PW_ADAPT", 1) != 0 ? 0u : 1u);   // (bit 0: the kernels do not shrink the claim on short queues — trace_w4.h)
+    grid = hinted_grid(c.queue_hint, grid, RSPT_TRACE_BLOCK);
+    uint32_t* n_overflow = c.cursor + 2;  // QueueCounts layout: overflow word sits two after its cursor
+    const uint32_t spill_rows = (uint32_t)std::min<size_t>(env_size("RSPT_W4_SPILL_ROWS", RSPT_W4_SPILL), RSPT_W4_SPILL);
+    if constexpr (INST) {
+        if (anim_w4) {   // moving instances; next to alpha-masked meshes the masks in line (ALPHA = 2) where every mask allows it, else through alpha_pass
+            // RSPT_PW_ENTER: lanes in front of an instance wait until that many of a wave do (trace_w4.h, the entry phase); it rides in bits 8.. of the leaf threshold
+            const int pw_enter = (int)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_ENTER", RSPT_PW_ENTER), 1), 64);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                                   c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, (p.leaf & 0xff) | (pw_enter << 8), s->w4_top, hi, xcur, pw_chunk);
+            };
+            if constexpr (ALPHA) { if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, true, 2, true>); else go(k_trace_w4<ANY, OUT_MODE, true, 1, true>); }
+            else go(k_trace_w4<ANY, OUT_MODE, true, 0, true>);
+            hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+            return;
+        }
+    }
+    if constexpr (ANY && !INST && !ALPHA) {
+        // round 6: shadow rays of plain scenes walk the 64-byte quantised records (trace_w4q.h; RSPT_ANY_Q=0: the plain kernel).  Occlusion flags byte-identical.
+        // Which of the two is faster depends on the rays, not on the scene's size: the quantised records win where the plain kernel is bound by L1 lane requests (C2's incoherent
+        // shadow rays through a dense soup: +6 % on the frame) and lose where it is bound by VALU issue with half its fetches in LDS (the C3 stand-in's coherent ones: -2.5 %;
+        // profiles/r06_any_q_ab.txt).  RSPT_ANY_Q=0 / 1 forces one; otherwise the scene's measured choice (rspt_scene_s::any_q_choice), the plain kernel until it exists.
+        const char* q_env = getenv("RSPT_ANY_Q");
+        const bool use_q = c.force_any_q >= 0 ? c.force_any_q != 0 : (q_env && *q_env ? atoi(q_env) != 0 : s->any_q_choice > 0);
+        if (use_q && which >= 2 && s->w4q && !(s->w4_root & RSPT_REF_LEAF) && c.ra == c.rb && env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) == 0 && !xcur && spill_rows == RSPT_W4_SPILL) {
+            hipLaunchKernelGGL((k_trace_w4q<OUT_MODE>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->w4q, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                               c.ra, c.occ, c.hits, reinterpret_cast<uint32_t*>(p.spill), p.refill, p.leaf, s->w4_top,
+                               pw_chunk | (env_size("RSPT_ANY_Q_LATE", 1) != 0 ? 2u : 0u) /* bit 1: the exact leaf-box test only behind a triangle hit (trace_w4q.h) */, s->leaf_boxes);
+            return;
+        }
+    }
+    if constexpr (!INST && !ALPHA) {
+        // RSPT_W4_SHAPE: 0 = five 256-thread workgroups per CU, 56 root-side records in LDS each; 1 = ONE 1024-thread workgroup per CU with 512 records;
+        // 2 = two 512-thread workgroups with 256 records each (trace_w4.h BLOCK / TOPCAP; dynamic LDS, 152 KB per CU either way)
+        const size_t shape = which >= 2 && s->w4_ok ? env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) : 0;
+        if (shape == 1 || shape == 2) {
+            auto go = [&](auto kern, uint32_t block, uint32_t topcap, uint32_t per_cu) -> bool {
+                const size_t lds = (size_t)8 * RSPT_W4_LDS * block + (size_t)112 * topcap;
+                static bool attr_set[2][2][2][3] = {};
+                bool& done = attr_set[ANY ? 1 : 0][OUT_MODE ? 1 : 0][0][shape];
+                static bool attr_bad[2][2][2][3] = {};
+                bool& bad = attr_bad[ANY ? 1 : 0][OUT_MODE ? 1 : 0][0][shape];
+                if (!done) { bad = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess; (void)hipGetLastError(); done = true; }
+                if (bad) return false;   // the device refuses that much dynamic LDS: the default shape serves the launch
+                const uint32_t bgrid = hinted_grid(c.queue_hint, grid_for(per_cu), block);
+                hipLaunchKernelGGL(kern, dim3(bgrid), dim3(block), lds, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                                   c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+                return true;
+            };
+            const bool launched = shape == 1 ? go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 1024, 512>, 1024u, 512u, 1u) : go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 512, 256>, 512u, 256u, 2u);
+            if (launched) {
+                if (trace_can_overflow(s))
+                    hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+                return;
+            }
+        }
+    }
+    if (ALPHA && s->alpha_simple)   // every mask of the scene is evaluated in line (kernels.h alpha_simple): the traversal keeps its register budget
+        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 2 : 0>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+    else if (special || (which >= 2 && s->w4_ok))
+        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 1 : 0>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+    else
+        hipLaunchKernelGGL((k_trace_pw<ANY, OUT_MODE>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->pairs, c.queue, c.count_ptr, c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf,
+                           p.refill, p.leaf);
+    // with every spill row in use the plain four-box kernel cannot overflow (RSPT_W4_MAX_STACK): no second pass to launch
+    if (trace_can_overflow(s))
+        hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+}
+// Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> with every spill row (a non-instanced four-box walk cannot then overflow, so no
+// k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q walks triangle
+// leaves only, and tune_any never measures them), no big-workgroup shapes: RSPT_COUNTERS, RSPT_TRACE_KERNEL, RSPT_ANY_Q, RSPT_W4_SHAPE and
+// RSPT_W4_SPILL_ROWS do not apply.  OUT_MODE 1 is the trace hook (main stream); OUT_MODE 0 the render's queues, on the stream the caller's lane
+// names with that lane's overflow list and spill rows (the two-stream shadow-ray overlap, RSPT_TRACE_STREAMS).  rspt_trace_device and
+// rspt_render check w4_ok first; rspt_render refuses RSPT_COUNTERS on sphere scenes.
+template <bool ANY, int OUT_MODE>
+void launch_trace_sph(const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur) {
+    const SceneDev& sc = s->dev;
+    const TracePre p = trace_pre(c, false);
+    uint32_t* n_overflow = c.cursor + 2;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
+                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, (uint32_t)RSPT_W4_SPILL, p.refill, p.leaf, s->w4_top, nullptr, xcur, p.chunk);
+    };
+    if (!s->has_alpha) go(k_trace_w4<ANY, OUT_MODE, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+    else go(k_trace_w4<ANY, OUT_MODE, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
+}
+template <bool ANY, int OUT_MODE>
+void launch_trace(uint32_t grid, const rspt_scene_s* s, const TraceCall& c) {
+    // XCD-affine dealing (trace_w4.h), RSPT_XCD_DEAL=1: available where the caller hands eight zeroed cursor words (the path integrator's loop, the trace hook).
+    // OFF by default: measured neutral to slightly negative (C2 474.0 -> 471.5 Msamples/s, C3 stand-in 2015.6 -> 2014.7; L2 hit rate of the closest-hit
+    // launches 0.624 -> 0.620 by TCC_HIT / TCC_MISS — profiles/r05_xcd_affine_ab.txt): the tree's L2 hits are its root side, which every XCD holds anyway
+    uint32_t* xcur = (c.xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? c.xcd_cursors : nullptr;
+    if (s->has_spheres) {   // ABI 23: the sphere instantiations (trace_w4.h SPH)
+        launch_trace_sph<ANY, OUT_MODE>(s, c, xcur);
+        return;
+    }
+    static void (*const variants[2][2])(uint32_t, const rspt_scene_s*, const TraceCall&, uint32_t*) = {{launch_trace_v<ANY, OUT_MODE, false, false>, launch_trace_v<ANY, OUT_MODE, false, true>}, {launch_trace_v<ANY, OUT_MODE, true, false>, launch_trace_v<ANY, OUT_MODE, true, true>}};
+    variants[s->has_instances][s->has_alpha](grid, s, c, xcur);
+}
+// ---- the shade stage's instantiations (kernels.h k_shade<F>) ----
+// A scene is served by the narrowest compiled feature set that covers what it can put in front of the stage (rspt_scene_s.shade_features
+// + the sampler): the code for every other lobe type, light kind, texture slot, instance transform and the Halton sampler folds away,
+// and with it registers (generic: 212 VGPRs = 2 waves / SIMD).  The arithmetic that remains is the same, so results do not change.
+// (the feature sets SV_DIFFUSE / SV_PLASTIC / SV_TEXTURED / SV_GENERIC: tu_decl.h, next to the instantiations they name)
+typedef void (*ShadeKernel)(RSPT_SHADE_ARGS);
+// natural = the compiler's own register budget; w3 / w4 = built for 3 / 4 waves per SIMD (amdgpu_waves_per_eu: what does not fit 168 / 128
+// VGPRs is spilled); dflt = which of the three runs.  Measured on one box (profiles/r03_ab_shade.md; Msamples/s of C2 / the C3 stand-in,
+// k_shade seconds per step): generic 212 VGPRs 423 / 1685 (0.161 / 0.578 s); diffuse 158 VGPRs = 3 waves as compiled 459 (0.111 s), forced to
+// 4 waves 455; plastic 173 VGPRs as compiled 1749 (0.531 s), 168 + 24 B of spills = 3 waves 1841 (0.470 s), 128 + 152 B = 4 waves 1791.
+struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */ };
+const ShadeVariant g_shade_variants[] = {
+    {SV_DIFFUSE, "diffuse", k_shade<SV_DIFFUSE>, k_shade_w<SV_DIFFUSE, 3>, k_shade_w<SV_DIFFUSE, 4>, 3, k_shade_mw<SV_DIFFUSE, 3>},   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
+                                                                                                           //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
+    {SV_PLASTIC, "plastic", k_shade<SV_PLASTIC>, k_shade_w<SV_PLASTIC, 3>, k_shade_w<SV_PLASTIC, 4>, 3, k_shade_mw<SV_PLASTIC, 3>},
+    {SV_TEXTURED, "textured", k_shade<SV_TEXTURED>, k_shade_w<SV_TEXTURED, 3>, k_shade_w<SV_TEXTURED, 4>, 0, k_shade_m<SV_TEXTURED>},
+    {SV_DIFFUSE_H, "diffuse-halton", k_shade<SV_DIFFUSE_H>, k_shade_w<SV_DIFFUSE_H, 3>, k_shade_w<SV_DIFFUSE_H, 3>, 3, k_shade_mw<SV_DIFFUSE_H, 3>},   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
+    {SV_PLASTIC_H, "plastic-halton", k_shade<SV_PLASTIC_H>, k_shade_w<SV_PLASTIC_H, 3>, k_shade_w<SV_PLASTIC_H, 3>, 3, k_shade_mw<SV_PLASTIC_H, 3>},
+    {SV_TEXTURED_H, "textured-halton", k_shade<SV_TEXTURED_H>, k_shade_w<SV_TEXTURED_H, 3>, k_shade_w<SV_TEXTURED_H, 3>, 3, k_shade_mw<SV_TEXTURED_H, 3>},   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
+    {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>},
+    {SV_DYNAMIC, "dynamic", k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, 0, nullptr},   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
+    {SF_ALL, "moving", k_shade<SF_ALL>, k_shade<SF_ALL>, k_shade<SF_ALL>, 0, nullptr},                     // + moving object instances (dev_scene.h inst_at)
+    // scenes with analytic spheres (SF_SPHERE; Sobol' and Halton): the generic / dynamic sets with the sphere arm (dev_bsdf.h shade_sph).  Only
+    // sphere scenes take them and sphere scenes take nothing else.  No MOVE form: sphere scenes keep slots for life (the recomputation reads the
+    // path's ray by slot).  As compiled: generic-sphere 224 VGPRs, 16 B of scratch, 2 waves / SIMD (generic: 221, 16 B, 2); dynamic-sphere 256 VGPRs
+    // + 1 AGPR, 320 B of scratch, ONE wave / SIMD (dynamic: 223, 304 B, 2) — a sphere scene with a dynamic material (a lobe list built per hit: a
+    // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
+    {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
+    {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
+};
+// RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
+// move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)
+ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
+    const char* force = getenv("RSPT_SHADE_VARIANT");
+    if (move_out) *move_out = nullptr;
+    const bool sph = (need & SF_SPHERE) != 0;
+    for (const ShadeVariant& v : g_shade_variants) {
+        if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
+        if ((need & ~v.features) != 0) continue;
+        if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;
+        if (name_out) *name_out = v.name;
+        const size_t waves = env_size("RSPT_SHADE_WAVES", (size_t)v.dflt);
+        if (move_out && waves == (size_t)v.dflt) *move_out = v.move;
+        return waves == 3 ? v.w3 : (waves == 4 ? v.w4 : v.natural);
+    }
+    if (sph) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)
+    return k_shade<SF_ALL>;
+}

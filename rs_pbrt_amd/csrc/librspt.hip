@@ -227,7 +227,7 @@ struct rspt_scene_s {
     const Quad4Node* w4q = nullptr;   // the same records on an 8-bit grid, for the shadow-ray kernel k_trace_w4q (trace_w4q.h): plain scenes only (no instances, no alpha masks)
     const float4* leaf_boxes = nullptr;  // [2 * first primitive of a leaf]: the leaf's LinearBVHNode bounds, for that kernel's exact leaf test
     int any_q_choice = -1;            // which kernel serves this scene's shadow rays: -1 not measured yet (the plain one until then), 0 k_trace_w4<true>, 1 k_trace_w4q — set by
-                                      // the first large shadow-ray launch of a render, which runs both on the same rays and keeps the faster (render_impl tune_any)
+                                      // the first large shadow-ray launch of a render, which runs both on the same rays and keeps the faster (RenderRun::tune_any)
     TexTables tex{};                  // textures / images / per-material slots (dev_texture.h); has_textures says whether set
     bool has_textures = false;
     // Lobe lists as material_assembly.h built them, once per value of the integrator's allow_multiple_lobes ([0]: true — path,
@@ -275,6 +275,17 @@ int dev_alloc(T** out, size_t n) {
     HIP_TRY(hipMalloc((void**)out, n * sizeof(T)));
     return RSPT_OK;
 }
+// a device array that only grows: free, null, zero the capacity, allocate, set the capacity
+template <class T, class N>
+int ensure_array(T** p, N* cap, size_t n) {
+    if (*cap >= n) return RSPT_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    int rc = dev_alloc(p, n);
+    if (rc) return rc;
+    *cap = (N)n;
+    return RSPT_OK;
+}
 template <class T>
 int upload(rspt_scene_s* s, const T* host, size_t n, const T** out) {
     *out = nullptr;
@@ -308,7 +319,7 @@ void free_paths() {
                     g.q[0][0], g.q[0][1], g.q[0][2], g.q[1][0], g.q[1][1], g.q[1][2]};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    if (g.path_time) (void)hipFree(g.path_time);   // sized with the path buffers (render_impl), freed with them
+    if (g.path_time) (void)hipFree(g.path_time);   // sized with the path buffers (RenderRun::prepare), freed with them
     g.path_time = nullptr; g.time_cap = 0;
     g.pb = PathBuf{};
     g.tex_rows = 0;
@@ -382,13 +393,7 @@ int ensure_tex_rows(bool dynamic) {
 }
 // dynamic materials: one Built record (8 lobes) per thread of the widest shade-stage launch
 int ensure_dyn_built(uint32_t threads) {
-    if (g.pb.dyn_built && g.pb.dyn_threads >= threads) return RSPT_OK;
-    if (g.pb.dyn_built) (void)hipFree(g.pb.dyn_built);
-    g.pb.dyn_built = nullptr; g.pb.dyn_threads = 0;
-    int rc = dev_alloc(&g.pb.dyn_built, threads);
-    if (rc) return rc;
-    g.pb.dyn_threads = threads;
-    return RSPT_OK;
+    return ensure_array(&g.pb.dyn_built, &g.pb.dyn_threads, threads);
 }
 
 int ensure_direct(size_t cap) {
@@ -427,34 +432,9 @@ int ensure_bins(size_t cap, uint32_t n_iters) {
         if ((rc = dev_alloc(&g.bin_keys, cap)) || (rc = dev_alloc(&g.q_sorted, cap + 64 * RSPT_BIN_K))) return rc;
         g.bin_cap = cap;
     }
-    if (g.n_bin_info < n_iters) {
-        if (g.bin_info) (void)hipFree(g.bin_info);
-        g.bin_info = nullptr; g.n_bin_info = 0;
-        if ((rc = dev_alloc(&g.bin_info, n_iters))) return rc;
-        g.n_bin_info = n_iters;
-    }
-    return RSPT_OK;
+    return ensure_array(&g.bin_info, &g.n_bin_info, n_iters);
 }
 
-int ensure_hit_inst(size_t n) {
-    if (g.hit_inst_cap >= n) return RSPT_OK;
-    if (g.hit_inst) (void)hipFree(g.hit_inst);
-    g.hit_inst = nullptr; g.hit_inst_cap = 0;
-    int rc = dev_alloc(&g.hit_inst, n);
-    if (rc) return rc;
-    g.hit_inst_cap = n;
-    return RSPT_OK;
-}
-
-int ensure_overflow_list(size_t n) {
-    if (g.ovf_cap >= n) return RSPT_OK;
-    if (g.ovf) (void)hipFree(g.ovf);
-    g.ovf = nullptr; g.ovf_cap = 0;
-    int rc = dev_alloc(&g.ovf, n);
-    if (rc) return rc;
-    g.ovf_cap = n;
-    return RSPT_OK;
-}
 
 int ensure_spill(size_t threads) {
     if (g.spill_threads >= threads) return RSPT_OK;
@@ -472,15 +452,6 @@ uint32_t pw_grid() { return grid_for((uint32_t)env_size("RSPT_PW_BLOCKS_PER_CU",
 // 1024 threads per CU of RSPT_W4_SHAPE = 1 / 2 — whichever is larger (with RSPT_PW_BLOCKS_PER_CU < 4 the big shapes indexed past the rows sized for the default)
 size_t pw_spill_threads() { return std::max<size_t>((size_t)pw_grid() * RSPT_PW_BLOCK, (size_t)grid_for(1) * 1024u); }
 
-int ensure_counts(uint32_t n) {
-    if (g.n_cnt >= n) return RSPT_OK;
-    if (g.cnt) (void)hipFree(g.cnt);
-    g.cnt = nullptr;
-    int rc = dev_alloc(&g.cnt, n);
-    if (rc) return rc;
-    g.n_cnt = n;
-    return RSPT_OK;
-}
 
 hipEvent_t get_event(size_t i) {
     while (g.events.size() <= i) {
@@ -575,1361 +546,22 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
     return RSPT_OK;
 }
 
-bool trace_can_overflow(const rspt_scene_s* s);
-// upper bound of the queue lengths of the launches that follow, when the host knows one (the null-surface tail of a render looks at
-// its queue every 8th iteration and the queues only shrink): a few hundred paths do not need 1280 persistent workgroups each copying
-// the root-side records into LDS
-uint32_t g_queue_hint = 0xffffffffu;
-uint32_t* g_inst_out = nullptr;  // where the next closest-hit launches record the instance of each hit instead of g.hit_inst (volpath's shadow-ray segments)
-uint32_t hinted_grid(uint32_t full, uint32_t per_block) {
-    if (g_queue_hint == 0xffffffffu) return full;
-    const uint64_t need = (2ull * g_queue_hint + per_block - 1) / per_block + 1;
-    return (uint32_t)std::min<uint64_t>(full, need);
-}
+// the render entry, included here once inside this namespace: one trace launch, the state of a render with its validation and setup, the schedules over it
+#include "launch_trace.h"
+#include "render_run.h"
+#include "render_schedules.h"
+#include "render_tile_serial.h"
 
-// kernel choice: the persistent-wave kernel (trace_wide.h) unless RSPT_TRACE_KERNEL=0 or the
-// reference-order node / triangle counters are wanted (only k_trace counts them)
-// lane 0 = the library's main stream; lane 1 = the second stream with its own overflow list and spill rows
-// One launch of the traversal stage.  Kernel choice: scenes with object instances or alpha-masked meshes take the <INST, ALPHA>
-// instantiations (template flags, so that the plain kernels stay the ones measured in DESIGN.md); counters and RSPT_TRACE_KERNEL=0
-// use the reference-order loop; a scene whose records outgrow the four-box reference fields stays on the two-box kernel.
-#ifndef RSPT_PW_CHUNK_CAMERA_DEFAULT
-#define RSPT_PW_CHUNK_CAMERA_DEFAULT 1024   // measured on the C3 stand-in, same box, alternating: 256 -> 2025 / 2029, 1024 -> 2075 / 2070, 4096 -> 2024 / 2030, 16384 -> 1900 Msamples/s
-                                            // (C2: 473.9 / 473.3 / 471.1 at 256 / 1024 / 4096); the incoherent launches keep 256 (512: C3 2061 with the camera launch at 1024)
-#endif
-#ifndef RSPT_PW_REFILL_CAMERA_DEFAULT
-#define RSPT_PW_REFILL_CAMERA_DEFAULT 48   // a wave of coherent camera rays refills when three quarters of its lanes are idle (the incoherent launches: RSPT_PW_REFILL = 16)
-#endif
-#ifndef RSPT_PW_ENTER
-#define RSPT_PW_ENTER 24   // C5 stand-in, every instance moving (profiles/r06_c5_enter_sweep.txt): 1 -> 142, 8 -> 170, 16 -> 182, 24 -> 183, 32 -> 180 Msamples/s
-#endif
-bool g_camera_launch = false;
-int g_any_q_force = -1;   // render_impl's measurement of the two shadow-ray kernels (tune_any): 0 / 1 forces the plain / the quantised one for the launches in between
-template <bool ANY, int OUT_MODE, bool INST, bool ALPHA>
-void launch_trace_v(int lane, bool count, uint32_t grid, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
-                    const rspt_ray* ra, const rspt_ray* rb, float4* oa, float4* ob, uint32_t* occ, rspt_hit* hits, unsigned long long* counters, uint32_t* xcur) {
-    const SceneDev& sc = s->dev;
-    // RSPT_TRACE_KERNEL: 0 = k_trace (reference-order single-ray loop), 1 = k_trace_pw (persistent waves, two boxes
-    // per record), 2 = k_trace_w4 (persistent waves, four boxes per record; default).
-    // (A quad-per-ray variant with one coalesced 64-byte fetch per step was measured 35 % slower: the
-    //  replicated control flow made it VALU-bound with 16 rays per wave)
-    const size_t which = env_size("RSPT_TRACE_KERNEL", 2);
-    hipStream_t stream = lane ? g.stream2 : g.stream;
-    uint32_t* ovf = g.ovf + (lane ? 2 * g.ovf_cap / 3 : 0);
-    uint2* spill = g.spill + (lane ? g.spill_threads * RSPT_W4_SPILL : 0);
-    uint32_t* hi = (INST && OUT_MODE == 0 && !ANY) ? (g_inst_out ? g_inst_out : g.hit_inst) : nullptr;
-    const bool special = INST || ALPHA;
-    // moving instances: k_trace_w4<.., INST, 0, ANIM> (round 5; RSPT_ANIM_W4=0: the reference-order loop with the interpolation, as before)
-    const bool anim_w4 = s->has_animated && s->w4_ok && which >= 2 && env_size("RSPT_ANIM_W4", 1) != 0 && env_size("RSPT_INSTANCE_KERNEL", 1) != 0;   // (round 6: the reference-order loop serves moving instances next to masks too, so every A/B switch stays bit-exact)
-    const bool slow = count || which == 0 || (s->has_animated && !anim_w4) || (special && (!s->w4_ok || env_size("RSPT_INSTANCE_KERNEL", 1) == 0));
-    if (slow) {
-        if (INST && s->has_animated)   // moving instances (alone or next to alpha-masked meshes): the reference-order loop with the interpolation (its own instantiations; no node / triangle counters)
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, queue, count_ptr, count_imm, ra, rb, oa, ob, occ, hits, counters, hi);
-        else if (count)
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, true, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, queue, count_ptr, count_imm, ra, rb, oa, ob, occ, hits, counters, hi);
-        else
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, queue, count_ptr, count_imm, ra, rb, oa, ob, occ, hits, counters, hi);
-        return;
-    }
-    const uint32_t pgrid = hinted_grid(pw_grid(), RSPT_PW_BLOCK);
-    // rays a wave claims per global atomic: 256 for the incoherent launches; the camera-ray launch of a batch (pixel-major queue: a chunk is a run of samples of one pixel
-    // or its neighbours) takes RSPT_PW_CHUNK_CAMERA (g_camera_launch is set around that launch by the path integrator's loop)
-    // refill / leaf-phase thresholds; the camera-ray launch may take its own (RSPT_PW_REFILL_CAMERA / RSPT_PW_LEAF_CAMERA: coherent rays reach their leaves together)
-    // (camera launch, C3 stand-in, one box, alternating: refill 16 -> 2079 / 2067 Msamples/s, 32 -> 2083 / 2083, 48 -> 2114 / 2113, 64 -> 2105 / 2101; leaf 16 / 24 / 32 at refill 16: 2061 / 2059 / 2046)
-    const int pw_refill = (int)(g_camera_launch ? env_size("RSPT_PW_REFILL_CAMERA", RSPT_PW_REFILL_CAMERA_DEFAULT) : env_size("RSPT_PW_REFILL", RSPT_PW_REFILL));
-    const int pw_leaf = (int)(g_camera_launch ? env_size("RSPT_PW_LEAF_CAMERA", env_size("RSPT_PW_LEAF", RSPT_PW_LEAF)) : env_size("RSPT_PW_LEAF", RSPT_PW_LEAF));
-    const uint32_t pw_chunk = (uint32_t)std::min<size_t>(std::max<size_t>((g_camera_launch ? env_size("RSPT_PW_CHUNK_CAMERA", RSPT_PW_CHUNK_CAMERA_DEFAULT) : env_size("RSPT_PW_CHUNK", RSPT_PW_CHUNK)) & ~(size_t)63, 64), 1u << 20) |
-                              (env_size("RSPT_PW_ADAPT", 1) != 0 ? 0u : 1u);   // (bit 0: the kernels do not shrink the claim on short queues — trace_w4.h)
-    grid = hinted_grid(grid, RSPT_TRACE_BLOCK);
-    uint32_t* n_overflow = cursor + 2;  // QueueCounts layout: overflow word sits two after its cursor
-    const uint32_t spill_rows = (uint32_t)std::min<size_t>(env_size("RSPT_W4_SPILL_ROWS", RSPT_W4_SPILL), RSPT_W4_SPILL);
-    if constexpr (INST) {
-        if (anim_w4) {   // moving instances; next to alpha-masked meshes the masks in line (ALPHA = 2) where every mask allows it, else through alpha_pass
-            // RSPT_PW_ENTER: lanes in front of an instance wait until that many of a wave do (trace_w4.h, the entry phase); it rides in bits 8.. of the leaf threshold
-            const int pw_enter = (int)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_ENTER", RSPT_PW_ENTER), 1), 64);
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                                   ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, spill_rows, pw_refill, (pw_leaf & 0xff) | (pw_enter << 8), s->w4_top, hi, xcur, pw_chunk);
-            };
-            if constexpr (ALPHA) { if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, true, 2, true>); else go(k_trace_w4<ANY, OUT_MODE, true, 1, true>); }
-            else go(k_trace_w4<ANY, OUT_MODE, true, 0, true>);
-            hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, n_overflow, ovf, ra, rb, oa, ob, occ, hits, hi);
-            return;
-        }
-    }
-    if constexpr (ANY && !INST && !ALPHA) {
-        // round 6: shadow rays of plain scenes walk the 64-byte quantised records (trace_w4q.h; RSPT_ANY_Q=0: the plain kernel).  Occlusion flags byte-identical.
-        // Which of the two is faster depends on the rays, not on the scene's size: the quantised records win where the plain kernel is bound by L1 lane requests (C2's incoherent
-        // shadow rays through a dense soup: +6 % on the frame) and lose where it is bound by VALU issue with half its fetches in LDS (the C3 stand-in's coherent ones: -2.5 %;
-        // profiles/r06_any_q_ab.txt).  RSPT_ANY_Q=0 / 1 forces one; otherwise the scene's measured choice (rspt_scene_s::any_q_choice), the plain kernel until it exists.
-        const char* q_env = getenv("RSPT_ANY_Q");
-        const bool use_q = g_any_q_force >= 0 ? g_any_q_force != 0 : (q_env && *q_env ? atoi(q_env) != 0 : s->any_q_choice > 0);
-        if (use_q && which >= 2 && s->w4q && !(s->w4_root & RSPT_REF_LEAF) && ra == rb && env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) == 0 && !xcur && spill_rows == RSPT_W4_SPILL) {
-            hipLaunchKernelGGL((k_trace_w4q<OUT_MODE>), dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->w4q, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                               ra, occ, hits, reinterpret_cast<uint32_t*>(spill), pw_refill, pw_leaf, s->w4_top,
-                               pw_chunk | (env_size("RSPT_ANY_Q_LATE", 1) != 0 ? 2u : 0u) /* bit 1: the exact leaf-box test only behind a triangle hit (trace_w4q.h) */, s->leaf_boxes);
-            return;
-        }
-    }
-    if constexpr (!INST && !ALPHA) {
-        // RSPT_W4_SHAPE: 0 = five 256-thread workgroups per CU, 56 root-side records in LDS each; 1 = ONE 1024-thread workgroup per CU with 512 records;
-        // 2 = two 512-thread workgroups with 256 records each (trace_w4.h BLOCK / TOPCAP; dynamic LDS, 152 KB per CU either way)
-        const size_t shape = which >= 2 && s->w4_ok ? env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) : 0;
-        if (shape == 1 || shape == 2) {
-            auto go = [&](auto kern, uint32_t block, uint32_t topcap, uint32_t per_cu) -> bool {
-                const size_t lds = (size_t)8 * RSPT_W4_LDS * block + (size_t)112 * topcap;
-                static bool attr_set[2][2][2][3] = {};
-                bool& done = attr_set[ANY ? 1 : 0][OUT_MODE ? 1 : 0][0][shape];
-                static bool attr_bad[2][2][2][3] = {};
-                bool& bad = attr_bad[ANY ? 1 : 0][OUT_MODE ? 1 : 0][0][shape];
-                if (!done) { bad = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess; (void)hipGetLastError(); done = true; }
-                if (bad) return false;   // the device refuses that much dynamic LDS: the default shape serves the launch
-                const uint32_t bgrid = hinted_grid(grid_for(per_cu), block);
-                hipLaunchKernelGGL(kern, dim3(bgrid), dim3(block), lds, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                                   ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, spill_rows, pw_refill, pw_leaf, s->w4_top, hi, xcur, pw_chunk);
-                return true;
-            };
-            const bool launched = shape == 1 ? go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 1024, 512>, 1024u, 512u, 1u) : go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 512, 256>, 512u, 256u, 2u);
-            if (launched) {
-                if (trace_can_overflow(s))
-                    hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, n_overflow, ovf, ra, rb, oa, ob, occ, hits, hi);
-                return;
-            }
-        }
-    }
-    if (ALPHA && s->alpha_simple)   // every mask of the scene is evaluated in line (kernels.h alpha_simple): the traversal keeps its register budget
-        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 2 : 0>), dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                           ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, spill_rows, pw_refill, pw_leaf, s->w4_top, hi, xcur, pw_chunk);
-    else if (special || (which >= 2 && s->w4_ok))
-        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 1 : 0>), dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                           ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, spill_rows, pw_refill, pw_leaf, s->w4_top, hi, xcur, pw_chunk);
-    else
-        hipLaunchKernelGGL((k_trace_pw<ANY, OUT_MODE>), dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->pairs, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, n_overflow, ovf,
-                           pw_refill, pw_leaf);
-    // with every spill row in use the plain four-box kernel cannot overflow (RSPT_W4_MAX_STACK): no second pass to launch
-    if (trace_can_overflow(s))
-        hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, stream, sc, s->tex, n_overflow, ovf, ra, rb, oa, ob, occ, hits, hi);
-}
-// Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> with every spill row (a non-instanced four-box walk cannot then overflow, so no
-// k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q walks triangle
-// leaves only, and tune_any never measures them), no big-workgroup shapes: RSPT_COUNTERS, RSPT_TRACE_KERNEL, RSPT_ANY_Q, RSPT_W4_SHAPE and
-// RSPT_W4_SPILL_ROWS do not apply.  OUT_MODE 1 is the trace hook (main stream); OUT_MODE 0 the render's queues, on the stream the caller's lane
-// names with that lane's overflow list and spill rows (the two-stream shadow-ray overlap, RSPT_TRACE_STREAMS).  rspt_trace_device and
-// rspt_render check w4_ok first; rspt_render refuses RSPT_COUNTERS on sphere scenes.
-template <bool ANY, int OUT_MODE>
-void launch_trace_sph(int lane, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
-                      const rspt_ray* ra, const rspt_ray* rb, float4* oa, float4* ob, uint32_t* occ, rspt_hit* hits, uint32_t* xcur) {
-    const SceneDev& sc = s->dev;
-    hipStream_t stream = lane ? g.stream2 : g.stream;
-    uint32_t* ovf = g.ovf + (lane ? 2 * g.ovf_cap / 3 : 0);
-    uint2* spill = g.spill + (lane ? g.spill_threads * RSPT_W4_SPILL : 0);
-    const uint32_t pgrid = hinted_grid(pw_grid(), RSPT_PW_BLOCK);
-    const int pw_refill = (int)env_size("RSPT_PW_REFILL", RSPT_PW_REFILL), pw_leaf = (int)env_size("RSPT_PW_LEAF", RSPT_PW_LEAF);
-    const uint32_t pw_chunk = (uint32_t)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_CHUNK", RSPT_PW_CHUNK) & ~(size_t)63, 64), 1u << 20);
-    uint32_t* n_overflow = cursor + 2;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(pgrid), dim3(RSPT_PW_BLOCK), 0, stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, queue, count_ptr, count_imm, cursor,
-                           ra, rb, oa, ob, occ, hits, n_overflow, ovf, spill, (uint32_t)RSPT_W4_SPILL, pw_refill, pw_leaf, s->w4_top, nullptr, xcur, pw_chunk);
-    };
-    if (!s->has_alpha) go(k_trace_w4<ANY, OUT_MODE, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
-    else if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
-    else go(k_trace_w4<ANY, OUT_MODE, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
-}
-template <bool ANY, int OUT_MODE>
-void launch_trace(int lane, bool count, uint32_t grid, const rspt_scene_s* s, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm, uint32_t* cursor,
-                  const rspt_ray* ra, const rspt_ray* rb, float4* oa, float4* ob, uint32_t* occ, rspt_hit* hits, unsigned long long* counters, uint32_t* xcd_cursors = nullptr) {
-    // XCD-affine dealing (trace_w4.h), RSPT_XCD_DEAL=1: available where the caller hands eight zeroed cursor words (the path integrator's loop, the trace hook).
-    // OFF by default: measured neutral to slightly negative (C2 474.0 -> 471.5 Msamples/s, C3 stand-in 2015.6 -> 2014.7; L2 hit rate of the closest-hit
-    // launches 0.624 -> 0.620 by TCC_HIT / TCC_MISS — profiles/r05_xcd_affine_ab.txt): the tree's L2 hits are its root side, which every XCD holds anyway
-    uint32_t* xcur = (xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? xcd_cursors : nullptr;
-    if (s->has_spheres) {   // ABI 23: the sphere instantiations (trace_w4.h SPH)
-        launch_trace_sph<ANY, OUT_MODE>(lane, s, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, xcur);
-        return;
-    }
-#define RSPT_LT(I, A) launch_trace_v<ANY, OUT_MODE, I, A>(lane, count, grid, s, queue, count_ptr, count_imm, cursor, ra, rb, oa, ob, occ, hits, counters, xcur)
-    if (s->has_instances) { if (s->has_alpha) RSPT_LT(true, true); else RSPT_LT(true, false); }
-    else { if (s->has_alpha) RSPT_LT(false, true); else RSPT_LT(false, false); }
-#undef RSPT_LT
-}
-
-// does the production trace kernel ever hand rays to k_trace_fixup?  Not the four-box kernel with all its spill rows (RSPT_W4_MAX_STACK)
-bool trace_can_overflow(const rspt_scene_s* s) {
-    const size_t which = env_size("RSPT_TRACE_KERNEL", 2);
-    const size_t rows = std::min<size_t>(env_size("RSPT_W4_SPILL_ROWS", RSPT_W4_SPILL), RSPT_W4_SPILL);
-    return s->has_instances || (s->has_alpha && !s->w4_ok) || !(which >= 2 && s->w4_ok) || RSPT_W4_LDS + rows < RSPT_W4_MAX_STACK;  // (two stacked aggregates + leaf continuations can pass the bound)
-}
-uint32_t trace_grid() { return grid_for((uint32_t)env_size("RSPT_TRACE_BLOCKS_PER_CU", 5)); }
-
-// ---- the shade stage's instantiations (kernels.h k_shade<F>) ----
-// A scene is served by the narrowest compiled feature set that covers what it can put in front of the stage (rspt_scene_s.shade_features
-// + the sampler): the code for every other lobe type, light kind, texture slot, instance transform and the Halton sampler folds away,
-// and with it registers (generic: 212 VGPRs = 2 waves / SIMD).  The arithmetic that remains is the same, so results do not change.
-// (the feature sets SV_DIFFUSE / SV_PLASTIC / SV_TEXTURED / SV_GENERIC: tu_decl.h, next to the instantiations they name)
-typedef void (*ShadeKernel)(RSPT_SHADE_ARGS);
-// natural = the compiler's own register budget; w3 / w4 = built for 3 / 4 waves per SIMD (amdgpu_waves_per_eu: what does not fit 168 / 128
-// VGPRs is spilled); dflt = which of the three runs.  Measured on one box (profiles/r03_ab_shade.md; Msamples/s of C2 / the C3 stand-in,
-// k_shade seconds per step): generic 212 VGPRs 423 / 1685 (0.161 / 0.578 s); diffuse 158 VGPRs = 3 waves as compiled 459 (0.111 s), forced to
-// 4 waves 455; plastic 173 VGPRs as compiled 1749 (0.531 s), 168 + 24 B of spills = 3 waves 1841 (0.470 s), 128 + 152 B = 4 waves 1791.
-struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */ };
-const ShadeVariant g_shade_variants[] = {
-    {SV_DIFFUSE, "diffuse", k_shade<SV_DIFFUSE>, k_shade_w<SV_DIFFUSE, 3>, k_shade_w<SV_DIFFUSE, 4>, 3, k_shade_mw<SV_DIFFUSE, 3>},   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
-                                                                                                           //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
-    {SV_PLASTIC, "plastic", k_shade<SV_PLASTIC>, k_shade_w<SV_PLASTIC, 3>, k_shade_w<SV_PLASTIC, 4>, 3, k_shade_mw<SV_PLASTIC, 3>},
-    {SV_TEXTURED, "textured", k_shade<SV_TEXTURED>, k_shade_w<SV_TEXTURED, 3>, k_shade_w<SV_TEXTURED, 4>, 0, k_shade_m<SV_TEXTURED>},
-    {SV_DIFFUSE_H, "diffuse-halton", k_shade<SV_DIFFUSE_H>, k_shade_w<SV_DIFFUSE_H, 3>, k_shade_w<SV_DIFFUSE_H, 3>, 3, k_shade_mw<SV_DIFFUSE_H, 3>},   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
-    {SV_PLASTIC_H, "plastic-halton", k_shade<SV_PLASTIC_H>, k_shade_w<SV_PLASTIC_H, 3>, k_shade_w<SV_PLASTIC_H, 3>, 3, k_shade_mw<SV_PLASTIC_H, 3>},
-    {SV_TEXTURED_H, "textured-halton", k_shade<SV_TEXTURED_H>, k_shade_w<SV_TEXTURED_H, 3>, k_shade_w<SV_TEXTURED_H, 3>, 3, k_shade_mw<SV_TEXTURED_H, 3>},   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
-    {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>},
-    {SV_DYNAMIC, "dynamic", k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, 0, nullptr},   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
-    {SF_ALL, "moving", k_shade<SF_ALL>, k_shade<SF_ALL>, k_shade<SF_ALL>, 0, nullptr},                     // + moving object instances (dev_scene.h inst_at)
-    // scenes with analytic spheres (SF_SPHERE; Sobol' and Halton): the generic / dynamic sets with the sphere arm (dev_bsdf.h shade_sph).  Only
-    // sphere scenes take them and sphere scenes take nothing else.  No MOVE form: sphere scenes keep slots for life (the recomputation reads the
-    // path's ray by slot).  As compiled: generic-sphere 224 VGPRs, 16 B of scratch, 2 waves / SIMD (generic: 221, 16 B, 2); dynamic-sphere 256 VGPRs
-    // + 1 AGPR, 320 B of scratch, ONE wave / SIMD (dynamic: 223, 304 B, 2) — a sphere scene with a dynamic material (a lobe list built per hit: a
-    // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
-    {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
-    {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
-};
-// RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
-// move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)
-ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
-    const char* force = getenv("RSPT_SHADE_VARIANT");
-    if (move_out) *move_out = nullptr;
-    const bool sph = (need & SF_SPHERE) != 0;
-    for (const ShadeVariant& v : g_shade_variants) {
-        if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
-        if ((need & ~v.features) != 0) continue;
-        if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;
-        if (name_out) *name_out = v.name;
-        const size_t waves = env_size("RSPT_SHADE_WAVES", (size_t)v.dflt);
-        if (move_out && waves == (size_t)v.dflt) *move_out = v.move;
-        return waves == 3 ? v.w3 : (waves == 4 ? v.w4 : v.natural);
-    }
-    if (sph) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)
-    return k_shade<SF_ALL>;
-}
-
-#ifndef RSPT_DL_WAVES_DEFAULT
-#define RSPT_DL_WAVES_DEFAULT 0
-#endif
-constexpr int RSPT_DL_RETRY_LANE = -1000;   // batch_direct -> the batch loop: redo this batch with the per-lane form (never leaves render_impl)
 int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, void* film_dev, float* li_host, rspt_stats* stats) {
-    if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
-    if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
-    // Analytic spheres are served as surfaces (hit, shaded, textured, blocking light) by the path and AO integrators in their wavefront form
-    // (Sobol' / Halton).  Everything else that holds a sphere is refused, so the caller keeps its CPU loop: sphere area lights (their
-    // sample_with_ref_point / pdf_with_ref_point and power are not on the device), the directlighting / whitted / volpath forms and the pixel
-    // samplers (their per-lane walks, trace_serial.h, have no sphere test), and a sphere scene whose records outgrow the four-box kernel.
-    if (s->has_spheres) {
-        static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
-        const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
-        if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: sphere area lights are not served on the device yet (%s)", iname);
-        if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
-            return fail(RSPT_E_UNSUPPORTED, "scene with spheres under the %s integrator: spheres are served by path and ao only", iname);
-        if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
-            return fail(RSPT_E_UNSUPPORTED, "scene with spheres under the %s sampler: spheres are served with the sobol and halton samplers only",
-                        d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
-                        d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
-        if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "sphere scene with more four-box records than a reference holds");
-        if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with spheres: the sphere traversal keeps no node counters");
-    }
-    // WhittedIntegrator::li runs on directlighting's machinery (direct.h / dl_serial.h, their WH forms) as UniformSampleAll with one estimate per light and
-    // no sample arrays; max_depth 0 recurses no more than 1 does (whitted.rs:103: depth + 1 < max_depth)
-    const bool whitted = d->integrator == RSPT_INTEGRATOR_WHITTED;
-    rspt_render_desc wd;
-    if (whitted) {
-        wd = *d;
-        wd.direct_strategy = RSPT_DIRECT_SAMPLE_ALL;
-        wd.n_light_samples = nullptr;
-        if (wd.max_depth == 0) wd.max_depth = 1;
-        d = &wd;
-    }
-    const char* dl_name = whitted ? "whitted" : "directlighting";
-    s->select_materials(d->integrator != RSPT_INTEGRATOR_DIRECT && !whitted);  // allow_multiple_lobes: false in DirectLightingIntegrator::li and WhittedIntegrator::li (directlighting.rs:86, whitted.rs:63)
-    const bool halton = d->sampler_kind == RSPT_SAMPLER_HALTON;
-    const bool sobol = d->sampler_kind == RSPT_SAMPLER_SOBOL;
-    const bool pixel_sampler = d->sampler_kind >= RSPT_SAMPLER_RANDOM && d->sampler_kind <= RSPT_SAMPLER_MAXMINDIST;  // one serial chain per tile: tile_serial.h
-    if (!sobol && !halton && !pixel_sampler) return fail(RSPT_E_UNSUPPORTED, "sampler kind %u", d->sampler_kind);
-    if (d->spp <= 0 || d->spp > (1ll << 30) || (sobol && (d->spp & (d->spp - 1)) != 0)) return fail(RSPT_E_INVALID, "spp must be in [1, 2^30] (a power of two for sobol)");
-    if (d->tile_size == 0 || d->tile_size > 4096) return fail(RSPT_E_INVALID, "bad tile_size");
-    if (sobol && (!d->tables.sobol32 || !d->tables.vdc || !d->tables.vdc_inv)) return fail(RSPT_E_INVALID, "null sobol tables");
-    if (pixel_sampler) {
-        if (d->integrator == RSPT_INTEGRATOR_DIRECT && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL && (d->sampler_kind == RSPT_SAMPLER_ZEROTWO || d->sampler_kind == RSPT_SAMPLER_MAXMINDIST))
-            for (uint32_t i = 0; s && d->n_light_samples && i < s->dev.n_lights; i++)
-                if (d->n_light_samples[i] < 1 || (d->n_light_samples[i] & (d->n_light_samples[i] - 1)) != 0)
-                    return fail(RSPT_E_INVALID, "directlighting: n_light_samples[%u] must be a power of two with the 02sequence / maxmindist samplers (preprocess passes it through round_count, directlighting.rs:58-60)", i);
-        if (d->integrator == RSPT_INTEGRATOR_AO && (d->sampler_kind == RSPT_SAMPLER_ZEROTWO || d->sampler_kind == RSPT_SAMPLER_MAXMINDIST) && (d->ao_n_samples & (d->ao_n_samples - 1)) != 0)
-            return fail(RSPT_E_INVALID, "ao: nsamples must be a power of two with the 02sequence / maxmindist samplers (request_2d_array asserts round_count(n) == n, zerotwosequence.rs:187-193)");
-        if (d->tile_size > 255) return fail(RSPT_E_UNSUPPORTED, "tile_size > 255 with a pixel sampler");
-        if (d->spp > 65536 || d->pixel_dimensions > 64) return fail(RSPT_E_UNSUPPORTED, "pixel sampler: spp > 65536 or more than 64 sampled dimensions");
-        if (d->sampler_kind == RSPT_SAMPLER_STRATIFIED && (d->strat_x == 0 || d->strat_y == 0 || (int64_t)d->strat_x * d->strat_y != d->spp))
-            return fail(RSPT_E_INVALID, "stratified sampler: spp must equal strat_x * strat_y");
-        if (d->sampler_kind == RSPT_SAMPLER_MAXMINDIST && (!d->maxmin_c_pixel || (d->spp & (d->spp - 1)) != 0)) return fail(RSPT_E_INVALID, "maxmindist sampler: spp must be a power of two and maxmin_c_pixel given");
-    }
-    if (halton && !d->tables.halton_perms) return fail(RSPT_E_INVALID, "null halton permutation table");
-    if (!(d->filter_radius[0] > 0.0f) || !(d->filter_radius[1] > 0.0f)) return fail(RSPT_E_INVALID, "bad filter radius");
-    if (d->max_depth > 200) return fail(RSPT_E_UNSUPPORTED, "max_depth > 200");
-    if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO && d->integrator != RSPT_INTEGRATOR_DIRECT && d->integrator != RSPT_INTEGRATOR_VOLPATH && !whitted)
-        return fail(RSPT_E_UNSUPPORTED, "integrator %u (path, ao, directlighting, volpath and whitted only)", d->integrator);
-    const bool direct = d->integrator == RSPT_INTEGRATOR_DIRECT || whitted;   // (the directlighting forms; `whitted` picks their WH instantiations)
-    const bool volpath = d->integrator == RSPT_INTEGRATOR_VOLPATH;
-    // moving instances under the pixel samplers and in the per-lane directlighting: round 6 (k_tile_serial modes 5 - 8, k_lane_dl<.., ANIM>); dynamic materials next to them under a
-    // pixel sampler are the one combination left without an instantiation
-    if (s->has_animated && pixel_sampler && s->has_dynamic)
-        return fail(RSPT_E_UNSUPPORTED, "a scene with a moving object instance AND a dynamic material (a lobe list that depends on a texture value) under a pixel sampler");
-    if (direct) {
-        if (d->max_depth < 1 || d->max_depth > (uint32_t)RSPT_DL_SERIAL_DEPTH)
-            return fail(RSPT_E_UNSUPPORTED, "%s: max_depth must be in [%d, %d] (the explicit recursion stack of the per-lane form, dl_serial.h)", dl_name, whitted ? 0 : 1, RSPT_DL_SERIAL_DEPTH);
-        if (whitted && s->dev.n_lights > (1u << 16)) return fail(RSPT_E_UNSUPPORTED, "whitted: more than 65536 lights (one estimate per light and node in one round, direct.h)");
-        if (d->direct_strategy > RSPT_DIRECT_SAMPLE_ONE) return fail(RSPT_E_INVALID, "bad direct_strategy");
-        for (uint32_t i = 0; s && d->n_light_samples && i < s->dev.n_lights; i++)
-            if (d->n_light_samples[i] < 1 || d->n_light_samples[i] > 4096) return fail(RSPT_E_INVALID, "n_light_samples[%u] out of range", i);
-    }
-    if (d->integrator == RSPT_INTEGRATOR_AO && (d->ao_n_samples == 0 || d->ao_n_samples > 4096)) return fail(RSPT_E_INVALID, "ao_n_samples must be in [1, 4096]");
-    // checkpoint / resume: the pixel samples [smp_begin, smp_end) of every pixel
-    const uint64_t smp_begin = d->sample_begin, smp_end = d->sample_count ? d->sample_begin + d->sample_count : (uint64_t)d->spp;
-    if (smp_begin >= smp_end || smp_end > (uint64_t)d->spp) return fail(RSPT_E_INVALID, "sample range [%llu, %llu) outside [0, spp)", (unsigned long long)smp_begin, (unsigned long long)smp_end);
-    if (pixel_sampler && (smp_begin != 0 || smp_end != (uint64_t)d->spp)) return fail(RSPT_E_UNSUPPORTED, "a pixel sampler renders all samples of a tile in one chain: partial sample ranges are not possible");
-    const int32_t* sb = d->sample_bounds;
-    const int32_t* cp = d->crop_px;
-    if (sb[2] <= sb[0] || sb[3] <= sb[1] || cp[2] <= cp[0] || cp[3] <= cp[1]) return fail(RSPT_E_INVALID, "empty sample or crop bounds");
-    if (sb[0] < -32768 || sb[1] < -32768 || sb[2] > 32767 || sb[3] > 32767) return fail(RSPT_E_UNSUPPORTED, "sample bounds outside the 16-bit pixel range");
-    const uint32_t shard_count = d->shard_count ? d->shard_count : 1, chunk = d->tile_chunk ? d->tile_chunk : 1;
-    if (d->shard_index >= shard_count) return fail(RSPT_E_INVALID, "shard_index >= shard_count");
-    // Sobol' needs 5 + 8 dims per bounce < 1024 (sobol.rs:119-124)
-    if (5ull + (volpath ? 10ull : 8ull) * (d->max_depth + 2ull) >= 1024ull) return fail(RSPT_E_UNSUPPORTED, "max_depth exceeds the 1024 Sobol' dimensions");
-
+    RenderRun r(s, d);
+    int rc;
+    if ((rc = r.validate())) return rc;
+    s->select_materials(r.multi_lobes);  // allow_multiple_lobes: false in DirectLightingIntegrator::li and WhittedIntegrator::li (directlighting.rs:86, whitted.rs:63)
     auto t_start = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(g.device));
-    int rc;
-    // ---- render constants ----
-    RenderDev rd{};
-    memcpy(rd.raster_to_camera, d->raster_to_camera, sizeof rd.raster_to_camera);
-    memcpy(rd.camera_to_world, d->camera_to_world, sizeof rd.camera_to_world);
-    rd.lens_radius = d->lens_radius; rd.focal_distance = d->focal_distance;
-    rd.cam_anim = nullptr;
-    if (d->camera_animated) {   // AnimatedTransform::new (camera_anim.h); equal key matrices = a camera that does not move
-        CamAnim ca;
-        if (camanim::camera_keys(d->camera_to_world, d->camera_time[0], d->camera_to_world_end, d->camera_time[1], &ca)) {
-            if (!g.cam_anim && (rc = dev_alloc(&g.cam_anim, 1))) return rc;
-            HIP_TRY(hipMemcpy(g.cam_anim, &ca, sizeof ca, hipMemcpyHostToDevice));
-            rd.cam_anim = g.cam_anim;
-        }
-    }
-    rd.shutter_open = d->shutter_open; rd.shutter_close = d->shutter_close;
-    memcpy(rd.sample_bounds, sb, sizeof rd.sample_bounds);
-    memcpy(rd.crop_px, cp, sizeof rd.crop_px);
-    rd.resolution = round_up_pow2_32(std::max(sb[2] - sb[0], sb[3] - sb[1]));  // sobol.rs:46-47
-    rd.log2_res = 31 - __builtin_clz((uint32_t)rd.resolution);
-    rd.spp = d->spp; rd.max_depth = d->max_depth; rd.rr_threshold = d->rr_threshold;
-    rd.filter_radius[0] = d->filter_radius[0]; rd.filter_radius[1] = d->filter_radius[1];
-    rd.max_sample_luminance = d->max_sample_luminance;
-    rd.tile_size = d->tile_size;
-    if (!g.sobol32) {
-        if ((rc = dev_alloc(&g.sobol32, 1024 * 52)) || (rc = dev_alloc(&g.vdc, 25 * 52)) || (rc = dev_alloc(&g.vdc_inv, 26 * 52)) || (rc = dev_alloc(&g.filter_table, 256))) return rc;
-    }
-    if (sobol) {
-        HIP_TRY(hipMemcpyAsync(g.sobol32, d->tables.sobol32, 1024 * 52 * 4, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync(g.vdc, d->tables.vdc, 25 * 52 * 8, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync(g.vdc_inv, d->tables.vdc_inv, 26 * 52 * 8, hipMemcpyHostToDevice, g.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(g.filter_table, d->filter_table, 256 * 4, hipMemcpyHostToDevice, g.stream));
-    rd.sobol32 = g.sobol32; rd.vdc = g.vdc; rd.vdc_inv = g.vdc_inv; rd.filter_table = g.filter_table;
-    rd.sampler_kind = d->sampler_kind;
-    rd.sample_at_pixel_center = d->sample_at_pixel_center;
-    uint32_t vol_dim_limit = 1024u;  // NUM_SOBOL_DIMENSIONS (sobol.rs:119-124) or the Halton permutation table the caller brought
-    if (halton) {  // HaltonSampler::new (halton.rs:80-131)
-        if (!g.primes) {  // PRIMES / PRIME_SUMS (lowdiscrepancy.rs:31-760)
-            std::vector<uint32_t> primes, sums;
-            for (uint32_t v = 2; primes.size() < 1000; v++) {
-                bool is_p = true;
-                for (uint32_t q = 2; q * q <= v; q++) if (v % q == 0) { is_p = false; break; }
-                if (is_p) primes.push_back(v);
-            }
-            uint32_t acc = 0;
-            for (uint32_t p : primes) { sums.push_back(acc); acc += p; }
-            g.host_primes = primes; g.host_prime_sums = sums;
-            if ((rc = dev_alloc(&g.primes, 1000)) || (rc = dev_alloc(&g.prime_sums, 1000))) return rc;
-            HIP_TRY(hipMemcpy(g.primes, primes.data(), 4000, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(g.prime_sums, sums.data(), 4000, hipMemcpyHostToDevice));
-        }
-        uint32_t max_dim = 5u + 8u * (d->max_depth + 2u);  // last dimension a path can consume, with slack
-        if (volpath) max_dim = std::min(990u, 5u + 10u * (d->max_depth + 2u) + 64u);  // 10 per counted bounce, 2 per uncounted pass through a medium boundary (slack for 32; vol.h cuts a path that needs more)
-        if (direct) {  // every dimension the caller's table covers: k_dl_assign reports a camera sample whose stream really ends beyond it
-            max_dim = 0;
-            while (max_dim + 1u < 1000u && (uint64_t)g.host_prime_sums[max_dim + 1u] + g.host_primes[max_dim + 1u] <= d->tables.n_halton_perms) max_dim++;
-        }
-        if (max_dim >= 1000u) return fail(RSPT_E_UNSUPPORTED, "max_depth exceeds the 1000 Halton dimensions");
-        const uint64_t need = (uint64_t)g.host_prime_sums[max_dim] + g.host_primes[max_dim];
-        if (d->tables.n_halton_perms < need) return fail(RSPT_E_INVALID, "halton permutation table has %llu entries, %llu needed for max_depth %u",
-                                                         (unsigned long long)d->tables.n_halton_perms, (unsigned long long)need, d->max_depth);
-        if (g.n_halton_perms < need) {
-            if (g.halton_perms) (void)hipFree(g.halton_perms);
-            g.halton_perms = nullptr; g.n_halton_perms = 0;
-            if ((rc = dev_alloc(&g.halton_perms, need))) return rc;
-            g.n_halton_perms = need;
-        }
-        HIP_TRY(hipMemcpyAsync(g.halton_perms, d->tables.halton_perms, need * sizeof(uint16_t), hipMemcpyHostToDevice, g.stream));
-        rd.halton_perms = g.halton_perms; rd.primes = g.primes; rd.prime_sums = g.prime_sums;
-        vol_dim_limit = max_dim;
-        const int32_t res[2] = {sb[2] - sb[0], sb[3] - sb[1]};
-        for (int i = 0; i < 2; i++) {
-            int32_t base = i == 0 ? 2 : 3, scale = 1, exp = 0;
-            while (scale < std::min(res[i], 128)) { scale *= base; exp += 1; }
-            rd.base_scales[i] = scale; rd.base_exponents[i] = exp;
-        }
-        rd.sample_stride = (uint64_t)rd.base_scales[0] * (uint64_t)rd.base_scales[1];
-        auto mult_inv = [](int64_t a, int64_t n) {  // multiplicative_inverse via extended_gcd (halton.rs:32-52)
-            int64_t x0 = 1, x1 = 0, r0 = a, r1 = n;
-            while (r1 != 0) {
-                int64_t q = r0 / r1, t = r0 - q * r1;
-                r0 = r1; r1 = t;
-                t = x0 - q * x1; x0 = x1; x1 = t;
-            }
-            int64_t m = x0 % n;
-            return (uint64_t)(m < 0 ? m + n : m);
-        };
-        rd.mult_inverse[0] = mult_inv(rd.base_scales[1], rd.base_scales[0]);
-        rd.mult_inverse[1] = mult_inv(rd.base_scales[0], rd.base_scales[1]);
-    }
-
-    LightDistDev ld;
-    const LightDist* ld_lazy = nullptr;  // on-demand voxels: a mark / build round in front of every shade launch
-    if ((rc = get_light_dist(s, d->light_strategy, &ld, &ld_lazy))) return rc;
-    // (k_ld_mark finds a hit's voxel from its barycentrics: a sphere scene takes the eager table or nothing)
-    if (ld_lazy && s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with spheres whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)");
-    if (volpath && s->dev.n_grid_media && !pixel_sampler)
-        return fail(RSPT_E_UNSUPPORTED, "volpath with a grid-density medium under the Sobol' / Halton sampler: every tracking step draws sampler dimensions (the reference panics past "
-                                        "dimension 1024 / 1000 within a bounce or two); render it with a pixel sampler (random / 02sequence / stratified / maxmindist)");
-    // on-demand voxels under volpath and the pixel samplers: their kernels meet the lookup points only while they run, so they claim missing
-    // voxels themselves (dev_scene.h light_row_try) and the step runs again once the claimed rows are built (lightdistrib.rs:276-384 builds on
-    // first touch too; a row is a pure function of (voxel, lights), Q18, so when it is built cannot show)
-    if (ld_lazy && (volpath || pixel_sampler)) { ld.lazy = reinterpret_cast<LightLazyWords*>(ld_lazy->lazy); ld.new_list = ld_lazy->new_list; }
-    static_assert(sizeof(LightLazyWords) == sizeof(LightLazy), "LightLazyWords mirrors LightLazy");
-    // the claimed voxels' rows: contributions of every light, the row's distribution, the table entries; returns how many were claimed
-    auto build_claimed_rows = [&](uint32_t* n_claimed) -> int {
-        LightLazy lz;
-        HIP_TRY(hipMemcpyAsync(g.look, ld_lazy->lazy, sizeof lz, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        memcpy(&lz, g.look, sizeof lz);
-        *n_claimed = lz.n_new;
-        if (lz.overflow) return fail(RSPT_E_NOMEM, "spatial light distribution: more than %u voxels were touched; raise RSPT_LIGHT_TABLE_POOL_BYTES", lz.max_rows);
-        if (lz.n_new == 0) return RSPT_OK;
-        const uint32_t lgrid = grid_for(4);
-        hipLaunchKernelGGL(k_ld_contrib_list, dim3(lgrid), dim3(256), 0, g.stream, s->dev, ld.nvox[0], ld.nvox[1], ld.nvox[2], ld_lazy->lazy, ld_lazy->new_list, ld_lazy->func);
-        hipLaunchKernelGGL(k_ld_build_list, dim3(lgrid), dim3(256), 0, g.stream, s->dev.n_lights, ld_lazy->lazy, ld_lazy->new_list, ld_lazy->func, ld_lazy->cdf, ld_lazy->func_int, ld_lazy->table);
-        hipLaunchKernelGGL(k_ld_commit, dim3(1), dim3(1), 0, g.stream, ld_lazy->lazy);
-        return RSPT_OK;
-    };
-
-    // ---- this shard's pixels: Morton-ordered tiles (blockqueue/mod.rs:23-52), row-major inside a tile ----
-    const int32_t ts = (int32_t)d->tile_size;
-    const int32_t ext_x = sb[2] - sb[0], ext_y = sb[3] - sb[1];
-    const int32_t ntx = (ext_x + ts - 1) / ts, nty = (ext_y + ts - 1) / ts;
-    std::vector<std::pair<uint32_t, uint32_t>> blocks((size_t)ntx * nty);
-    for (int32_t i = 0; i < ntx * nty; i++) blocks[i] = {(uint32_t)(i % ntx), (uint32_t)(i / ntx)};
-    std::stable_sort(blocks.begin(), blocks.end(), [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return morton2(a.first, a.second) < morton2(b.first, b.second); });
-    std::vector<uint32_t> pix;
-    pix.reserve((size_t)ext_x * ext_y / shard_count + 1024);
-    for (size_t i = 0; i < blocks.size(); i++) {
-        if ((i / chunk) % shard_count != d->shard_index) continue;
-        int32_t x0 = sb[0] + (int32_t)blocks[i].first * ts, x1 = std::min(x0 + ts, sb[2]);
-        int32_t y0 = sb[1] + (int32_t)blocks[i].second * ts, y1 = std::min(y0 + ts, sb[3]);
-        for (int32_t y = y0; y < y1; y++)
-            for (int32_t x = x0; x < x1; x++) pix.push_back(((uint32_t)(uint16_t)(int16_t)y << 16) | (uint32_t)(uint16_t)(int16_t)x);
-    }
-    const size_t n_pix = pix.size();
-    if (g.pix_cap < n_pix) {
-        if (g.pix_list) (void)hipFree(g.pix_list);
-        g.pix_list = nullptr; g.pix_cap = 0;
-        if ((rc = dev_alloc(&g.pix_list, n_pix))) return rc;
-        g.pix_cap = n_pix;
-    }
-    if (n_pix) HIP_TRY(hipMemcpyAsync(g.pix_list, pix.data(), n_pix * 4, hipMemcpyHostToDevice, g.stream));
-
-    // ---- film ----
-    const size_t film_px = (size_t)(cp[2] - cp[0]) * (size_t)(cp[3] - cp[1]);
-    if (g.film_px < film_px) {
-        for (float4** p : {&g.film_own, &g.film_splat, &g.film_out}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        g.film_px = 0;
-        if ((rc = dev_alloc(&g.film_own, film_px)) || (rc = dev_alloc(&g.film_splat, film_px)) || (rc = dev_alloc(&g.film_out, film_px))) return rc;
-        g.film_px = film_px;
-    }
-    HIP_TRY(hipMemsetAsync(g.film_own, 0, film_px * sizeof(float4), g.stream));
-    HIP_TRY(hipMemsetAsync(g.film_splat, 0, film_px * sizeof(float4), g.stream));
-    // the film stage: k_film, or for filters wider than a pixel the gather form (kernels.h k_film_gather; RSPT_FILM_GATHER=0: the atomic form)
-    const int film_k = (int)std::floor(std::max(d->filter_radius[0], d->filter_radius[1]) + 0.5f);
-    const bool film_gather = (d->filter_radius[0] > 0.5f || d->filter_radius[1] > 0.5f) && film_k <= 8 && env_size("RSPT_FILM_GATHER", 1) != 0;
-    const size_t sb_px = (size_t)(sb[2] - sb[0]) * (size_t)(sb[3] - sb[1]);
-    if (film_gather && g.pix_index_cap < sb_px) {
-        if (g.pix_index) (void)hipFree(g.pix_index);
-        g.pix_index = nullptr; g.pix_index_cap = 0;
-        if ((rc = dev_alloc(&g.pix_index, sb_px))) return rc;
-        g.pix_index_cap = sb_px;
-    }
-    auto film_index = [&](const uint32_t* list, uint32_t n) -> int {   // (the list a batch indexes: the render's, or one pass of the pixel samplers)
-        if (!film_gather) return RSPT_OK;
-        HIP_TRY(hipMemsetAsync(g.pix_index, 0xff, sb_px * sizeof(uint32_t), g.stream));
-        if (n) hipLaunchKernelGGL(k_pix_index, dim3((n + 255) / 256), dim3(256), 0, g.stream, list, n, sb[0], sb[1], sb[2] - sb[0], g.pix_index);
-        return RSPT_OK;
-    };
-    float* li_dev = nullptr;
-    auto film_stage = [&](const RenderDev& rd_, const Batch& bt, const PathBuf& fpb, const uint32_t* list) {
-        if (!film_gather) {
-            hipLaunchKernelGGL(k_film, dim3((bt.n_pix + 255) / 256), dim3(256), 0, g.stream, rd_, bt, fpb, list, g.film_own, (float*)g.film_splat, li_dev, g.totals + 5);
-            return;
-        }
-        const size_t s2 = (size_t)(RSPT_FG_T + 2 * film_k) * (RSPT_FG_T + 2 * film_k);
-        const size_t fit = (60000 - s2 * 4 - 1024) / (s2 * 24);   // sample rows of (chunk + 1) x 24 bytes per source pixel in < 64 KB of LDS
-        const uint32_t chunk = (uint32_t)std::min<size_t>(std::max<size_t>(fit, 2) - 1, 8);
-        const size_t lds = s2 * (chunk + 1) * 24 + s2 * 4 + 1024;
-        hipLaunchKernelGGL(k_film_gather, dim3((uint32_t)((sb[2] - sb[0] + RSPT_FG_T - 1) / RSPT_FG_T), (uint32_t)((sb[3] - sb[1] + RSPT_FG_T - 1) / RSPT_FG_T)), dim3(256), lds, g.stream,
-                           rd_, bt, fpb, g.pix_index, film_k, chunk, g.film_own, li_dev, g.totals + 5);
-    };
-    struct LiGuard { float** p; ~LiGuard() { if (*p) (void)hipFree(*p); } } li_guard{&li_dev};  // also on the early error returns below
-    if (li_host) {
-        HIP_TRY(hipMalloc((void**)&li_dev, film_px * (size_t)d->spp * 3 * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(li_dev, 0, film_px * (size_t)d->spp * 3 * sizeof(float), g.stream));
-    }
-
-    // ---- batches ----
-    // paths per wavefront batch: ~280 B of state each, so 2^29 paths = 150 GB of the 288 GB HBM.  Large batches keep the persistent
-    // trace kernel's queues long and its launches few (every launch ends in a tail of a few long rays): measured with round 1's
-    // kernels, 2^25 / 2^26 / 2^27 / 2^28 paths per batch = 367 / 386 / 398 / 405 Msamples/s on C2 and 1243 / 1400 / 1472 / 1525 on
-    // the C3 stand-in; with round 4's, 2^28 -> 2^29 on the C3 stand-in: 1929 -> 1966 (same box; C2's frame is 2^28 paths, one batch
-    // either way).  Halving the number of launch tails bought 1.9 %: what is left of them is what a second pipeline of half batches
-    // on other streams could still fill — less than that again, which is why shade / trace overlap across batches was not built
-    // (DESIGN.md section 10).  When the device cannot give that much (other tenants), the batch is halved until it fits.
-    size_t cap = env_size("RSPT_BATCH", (size_t)1 << 29);
-    cap = std::min<size_t>(std::max<size_t>(cap, 1024), (size_t)1 << 30);
-    const bool counters = env_size("RSPT_COUNTERS", 0) != 0;
-    // AOIntegrator: every camera sample carries ao_n_samples shadow rays through the same ray / occlusion arrays
-    const bool ao = d->integrator == RSPT_INTEGRATOR_AO;
-    const uint32_t ao_n = ao ? d->ao_n_samples : 1u;
-    if (ao) cap = std::max<size_t>(cap / ao_n, 1024);
-    // directlighting under Sobol' / Halton: the wavefront form (direct.h) unless the render needs what only the per-lane form has
-    // (lane_serial.h): textured materials, more than 8 recursion levels; RSPT_DL_FORM=lane forces it (A/B, tests)
-    const char* dl_form_env = getenv("RSPT_DL_FORM");
-    // levels of the specular tree that can hold nodes (direct.h DlBuf::levels): a scene without specular lobes has the root only
-    const bool dl_specular = s->has_dynamic || (s->shade_features & (RSPT_SF_LOBE(RSPT_BXDF_SPECULAR_R) | RSPT_SF_LOBE(RSPT_BXDF_SPECULAR_T) | RSPT_SF_LOBE(RSPT_BXDF_FRESNEL_SPEC))) != 0;
-    // round 6: textured materials WITHOUT specular lobes stay in the wavefront form (every node is a camera hit: k_dl_texture); with specular lobes the children's rays carry
-    // reflected / refracted differentials, which only the per-lane form tracks.  RSPT_DL_TEX_WAVEFRONT=0: textures always per lane, as before.  (The estimate kernel of the
-    // one-round form is the one that reads the texture results: RSPT_DL_ROUNDS=1 or more than 2^16 estimates per node also send a textured scene to the per-lane form.)
-    bool dl_rounds_one = whitted || env_size("RSPT_DL_ROUNDS", 0) == 0;   // (whitted's estimates exist in the one-round form only)
-    if (dl_rounds_one && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL && s->dev.n_lights) {
-        uint64_t r = 0;
-        for (uint32_t j = 0; j < s->dev.n_lights; j++) r += d->n_light_samples ? (uint64_t)std::max<int32_t>(d->n_light_samples[j], 0) : 1u;
-        if (r > (1u << 16)) dl_rounds_one = false;
-    }
-    const bool dl_tex_wave = s->has_textures && !dl_specular && dl_rounds_one && env_size("RSPT_DL_TEX_WAVEFRONT", 1) != 0;
-    bool dl_lane = direct && !pixel_sampler && ((s->has_textures && !dl_tex_wave) || d->max_depth > 8 || (dl_form_env && !strcmp(dl_form_env, "lane")));
-    const uint32_t dl_levels = (dl_specular || env_size("RSPT_DL_FULL_TREE", 0) != 0) ? (uint32_t)d->max_depth : std::min<uint32_t>((uint32_t)d->max_depth, 1u);
-    const uint32_t dl_H = (direct && !pixel_sampler && !dl_lane) ? (1u << dl_levels) : 1u;   // node slots per camera sample (direct.h; in the per-lane forms a lane walks the tree itself)
-    // all light estimates of a node in one round (direct.h k_dl_nee_all): R = sum_j n_j virtual slots per node slot in the ray / result arrays; RSPT_DL_ROUNDS=1 = one
-    // round per estimate as before (R = 1 for the sizing)
-    uint32_t dl_R = 1;
-    // (R used to be CLAMPED to 2^20 while the kernels iterate over the unclamped sum — virtual slots would alias.  A sum above 2^16 — hundreds of lights at thousands
-    //  of samples each — takes the round-per-estimate form instead, whose slots do not depend on it; n_slots * R then stays far below the RSPT_Q_MIS bit: the batch is <= 2^28 / R)
-    bool dl_one_round = direct && !pixel_sampler && !dl_lane && (whitted || env_size("RSPT_DL_ROUNDS", 0) == 0);
-    if (dl_one_round && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL && s->dev.n_lights) {
-        uint64_t r = 0;
-        for (uint32_t j = 0; j < s->dev.n_lights; j++) r += d->n_light_samples ? (uint64_t)std::max<int32_t>(d->n_light_samples[j], 0) : 1u;
-        if (r > (1u << 16)) dl_one_round = false;
-        else dl_R = (uint32_t)std::max<uint64_t>(r, 1u);
-    }
-    if (direct) cap = std::max<size_t>(std::min<size_t>(cap, (size_t)1 << (dl_lane ? (s->has_dynamic ? 20 : 22) : (dl_R > 1 ? 28 : 26))) / dl_H / dl_R, 1024);   // (per-lane form: texture rows and lobe records per recursion level)
-    if (pixel_sampler) cap = std::max<size_t>(blocks.size(), 1024);   // one path slot per tile (tile_serial.h); the samples' results have their own arrays
-    // round 6: the path integrator's MOVING path state (kernels.h PathBuf::move) — wherever the scene's shade instantiation has a MOVE form; not with moving instances
-    // (their ray times are kept by original slot) and not under the pixel samplers / the other integrators, which keep slots for life.  RSPT_MOVE=0: slots, as before.
-    const char* shade_name = "generic";
-    ShadeKernel shade_move_k = nullptr;
-    const ShadeKernel shade_slot_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k);
-    if (!shade_slot_k) return fail(RSPT_E_UNSUPPORTED, "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
-    const bool move = !volpath && !direct && !ao && !pixel_sampler && !s->has_animated && shade_move_k != nullptr && env_size("RSPT_MOVE", 1) != 0;
-    // the first iteration that runs the MOVE kernel.  Iteration 0 reads a dense pixel-major queue whatever the schedule and its stores are dense too (every slot is
-    // written): the slot-for-life kernel serves it (the MOVE form is 4 % slower there: 120 B of scratch against 36 at the same 168 VGPRs, profiles/r06_move_ab.txt),
-    // and the first MOVE launch reads what it left in place
-    const uint32_t move_first = (uint32_t)env_size("RSPT_MOVE_FROM", 1);
-    if (!move) free_move();   // (213 GB at the default batch: the second set is not kept for renders that do not use it)
-    uint32_t ns = 1;  // samples per pixel per batch: largest power of two with n_pix * ns <= cap
-    size_t pix_per_batch = 1;
-    for (;;) {
-        ns = 1;
-        while ((uint64_t)ns * 2 <= (uint64_t)d->spp && (uint64_t)n_pix * ns * 2 <= cap) ns *= 2;
-        pix_per_batch = std::max<size_t>(1, std::min(n_pix, cap / ns));
-        rc = ensure_paths(std::max<size_t>(pix_per_batch * ns, 1) * ao_n * dl_H * dl_R);
-        if (rc == RSPT_OK && direct && !pixel_sampler && !dl_lane) rc = ensure_direct(g.cap);
-        if (rc == RSPT_OK && volpath) rc = ensure_vol(g.cap);
-        if (rc == RSPT_OK && move) rc = ensure_move(g.cap);
-        if (rc == RSPT_OK) break;
-        (void)hipGetLastError();  // out of memory: clear the sticky error and try half the batch
-        free_paths();
-        if (cap <= ((size_t)1 << 20)) return rc;
-        cap /= 2;
-    }
-    // the per-lane directlighting forms: per-level texture rows, the light sample counts on the device, error / truncation words
-    struct TmpGuard { std::vector<void*> p; ~TmpGuard() { for (void* q : p) (void)hipFree(q); } } dl_guard;
-    float4* dl_tex = nullptr; int32_t* dl_nls = nullptr; uint32_t* dl_words = nullptr; rspt_mat::Built* dl_dyn = nullptr;
-    const uint32_t dl_tex_rows = RSPT_TEX_ROWS + (s->has_dynamic ? RSPT_DYN_ROWS : 0);
-    const size_t dl_lanes = pixel_sampler ? blocks.size() : pix_per_batch * ns;
-    if (direct) {
-        if (s->has_textures && (dl_lane || pixel_sampler)) {   // (the wavefront form over textures keeps its results in g.pb.tex; it cannot fall back to the per-lane form: that needs a specular lobe)
-            if ((rc = dev_alloc(&dl_tex, (size_t)d->max_depth * dl_tex_rows * std::max<size_t>(dl_lanes, 1)))) return rc;
-            dl_guard.p.push_back(dl_tex);
-            if (s->has_dynamic) {
-                if ((rc = dev_alloc(&dl_dyn, (size_t)d->max_depth * std::max<size_t>(dl_lanes, 1)))) return rc;
-                dl_guard.p.push_back(dl_dyn);
-            }
-        }
-        if (!pixel_sampler) {
-            if ((rc = dev_alloc(&dl_words, 2))) return rc;
-            dl_guard.p.push_back(dl_words);
-            if (d->n_light_samples && s->dev.n_lights) {
-                if ((rc = dev_alloc(&dl_nls, s->dev.n_lights))) return rc;
-                dl_guard.p.push_back(dl_nls);
-                HIP_TRY(hipMemcpy(dl_nls, d->n_light_samples, s->dev.n_lights * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-        }
-    }
-    const uint32_t nominal_iters = d->max_depth + 1;
-    // a pass through a null-material surface costs a wavefront iteration without counting as a bounce (path.rs:109-116 has no limit
-    // on them); the loop below runs until no path is left, and a scene that needs more than RSPT_NULL_PASSES extra iterations is
-    // reported, not silently truncated
-    const uint32_t max_iters = s->has_null_material ? nominal_iters + (uint32_t)env_size("RSPT_NULL_PASSES", 1024) : nominal_iters;
-    if (volpath) HIP_TRY(hipMemsetAsync(g.vol.truncated, 0, sizeof(uint32_t), g.stream));
-    // K7b: whole waves of one class (escaped | depth limit | material) for k_shade.  C3 stand-in (two materials): 1396 -> 1686 Msamples/s;
-    // C2 (one material: only the escaped paths are separated): 423 -> 425
-    // (measured with the specialised shade instantiations, profiles/r03_ab_shade.md: C3 stand-in — plastic statue on a matte ground — 1640 -> 1830
-    //  Msamples/s with the bins; C2 — one material, only escaped paths to separate — 468 -> 456: the sort runs when lobe lists differ)
-    const bool shade_bins = env_size("RSPT_SHADE_BINS", s->shade_classes > 1 ? 1 : 0) != 0 && !ao && !direct && !volpath;
-    if (shade_bins && (rc = ensure_bins(g.cap, max_iters + 10))) return rc;
-    // iteration 0 (camera rays) arrives in pixel-major order — neighbouring slots, neighbouring pixels, mostly one material per wave already —
-    // and has the longest queue of the batch: it is left unsorted (same box, alternating: C3 stand-in 1855 -> 1906 Msamples/s, textured
-    // 1319 -> 1339; RSPT_BIN_FIRST=1 sorts it as before)
-    const bool bins_first = env_size("RSPT_BIN_FIRST", 0) != 0;
-    if (s->has_instances && (rc = ensure_hit_inst(volpath ? 2 * g.cap : g.cap))) return rc;   // volpath: second half = the hits of the shadow-ray segments
-    // moving instances: every path keeps its ray time (the camera sample's), read where an instance's Transform is interpolated
-    if (s->has_animated) {
-        if (g.time_cap < g.cap) {
-            if (g.path_time) (void)hipFree(g.path_time);
-            g.path_time = nullptr; g.time_cap = 0;
-            if ((rc = dev_alloc(&g.path_time, g.cap))) return rc;
-            g.time_cap = g.cap;
-        }
-    }
-    g.pb.time = s->has_animated ? g.path_time : nullptr;
-    s->dev.ray_time = g.pb.time;
-    s->dev.time_div = 1u;
-    g.pb.fresh = 0u;
-    g.pb.hit_inst = s->has_instances ? g.hit_inst : nullptr;
-    g.vol.hit_inst_tr = (volpath && s->has_instances) ? g.hit_inst + g.cap : nullptr;
-    if ((rc = ensure_counts(max_iters + 10)) || (rc = ensure_overflow_list(trace_can_overflow(s) ? 3 * g.cap : 1024)) || (rc = ensure_spill(pw_spill_threads())) ||
-        (s->has_textures && (rc = ensure_tex_rows(s->has_dynamic)))) return rc;
-    if (!g.totals) { if ((rc = dev_alloc(&g.totals, 8))) return rc; }
-    HIP_TRY(hipMemsetAsync(g.totals, 0, 8 * sizeof(unsigned long long), g.stream));
-
-    // LDS copy of the Sobol' matrices for k_shade: dimensions 0 .. 5 + 8 per bounce (+8 of read-ahead), index bits
-    // 2*log2(resolution) + log2(spp) (lowdiscrepancy.rs:1014-1043); the checks above keep this under 64 KB
-    const uint32_t sob_nd = 5u + 8u * (d->max_depth + 2u) + 8u;
-    uint32_t sob_bits = 2u * (uint32_t)rd.log2_res;
-    for (int64_t v = d->spp; v > 1; v >>= 1) sob_bits++;
-    sob_bits = std::min(52u, sob_bits + 1u);
-    if ((size_t)sob_nd * sob_bits * 4 > 64 * 1024) return fail(RSPT_E_UNSUPPORTED, "max_depth %u x %u index bits exceed the LDS Sobol' table", d->max_depth, sob_bits);
-    const uint32_t tgrid = trace_grid();
-    const ShadeKernel shade_k = shade_slot_k;   // (iterations >= move_first of a MOVE render launch shade_move_k)
-    if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: shade stage instantiation '%s'%s (scene features %#x)\n", shade_name, move ? ", moving path state" : "", s->shade_features);
-    // one launch fills the chip once: as many 256-thread blocks per CU as the instantiation's registers and the LDS table allow
-    int shade_blocks = 2;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&shade_blocks, reinterpret_cast<const void*>(shade_k), 256, sob_nd * sob_bits * sizeof(uint32_t)) != hipSuccess || shade_blocks < 1) {
-        (void)hipGetLastError();
-        shade_blocks = 2;
-    }
-    const uint32_t sgrid = grid_for((uint32_t)env_size("RSPT_SHADE_BLOCKS_PER_CU", (size_t)shade_blocks));
-    if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: shade stage: %d blocks of 256 per CU\n", shade_blocks);
-    // dynamic materials: one Built record per thread of the widest shade-stage launch (k_shade's grid; k_vol_shade runs grid_for(4))
-    if (s->has_dynamic && (rc = ensure_dyn_built(std::max(sgrid, grid_for(8)) * 256u))) return rc;
-    size_t n_ev = 0;
-    const bool two_streams = env_size("RSPT_TRACE_STREAMS", 2) >= 2 && !counters;
-    hipEvent_t ev_fork = get_event(n_ev++), ev_join = get_event(n_ev++);
-    uint64_t trace_launches = 0;
-    hipEvent_t ev_k0 = get_event(n_ev++), ev_k1 = get_event(n_ev++);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_ev;
-    // per-launch durations, each pair recorded on the stream its kernel runs on (closest-hit, shadow-ray, shade [+ texture])
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev[3];
-    auto ev_open = [&](int kind, int lane) {
-        hipEvent_t a = get_event(n_ev++), b = get_event(n_ev++);
-        (void)hipEventRecord(a, lane ? g.stream2 : g.stream);
-        kev[kind].push_back({a, b});
-    };
-    auto ev_close = [&](int kind, int lane) { (void)hipEventRecord(kev[kind].back().second, lane ? g.stream2 : g.stream); };
-    HIP_TRY(hipEventRecord(ev_k0, g.stream));
-    uint64_t samples = 0, truncated = 0, vol_rays = 0;
-    // ---- one batch of each integrator (the wavefront schedules); `it` leaves with the number of queue-counter records used ----
-    // Which kernel serves this scene's shadow rays (trace_w4q.h; launch_trace_v): measured once per scene, by the first shadow-ray launch of a batch of >= 2^22 paths — both kernels
-    // run on the same rays (their flags are identical), the faster one is kept in rspt_scene_s::any_q_choice.  Returns 1 if it made the launch (twice), 0 if there was nothing to
-    // measure (the caller launches as usual), -code on an error.
-    auto tune_any = [&](uint32_t batch_n, const uint32_t* queue, uint32_t* count_ptr, uint32_t* cursor, const rspt_ray* rays, uint32_t* occ, uint32_t* xcd) -> int {
-        if (!s->w4q || s->any_q_choice >= 0 || getenv("RSPT_ANY_Q") || counters || batch_n < (1u << 22) || env_size("RSPT_ANY_Q_TUNE", 1) == 0) return 0;
-        hipEvent_t t0 = get_event(n_ev++), t1 = get_event(n_ev++), t2 = get_event(n_ev++);
-        if (hipEventRecord(t0, g.stream) != hipSuccess) return RSPT_E_HIP;
-        g_any_q_force = 0;
-        launch_trace<true, 0>(0, false, tgrid, s, queue, count_ptr, 0, cursor, rays, rays, nullptr, nullptr, occ, nullptr, g.totals, xcd);
-        (void)hipEventRecord(t1, g.stream);
-        (void)hipMemsetAsync(cursor, 0, sizeof(uint32_t), g.stream);   // (the persistent kernel's fetch cursor: the second run starts over)
-        g_any_q_force = 1;
-        launch_trace<true, 0>(0, false, tgrid, s, queue, count_ptr, 0, cursor, rays, rays, nullptr, nullptr, occ, nullptr, g.totals, xcd);
-        g_any_q_force = -1;
-        (void)hipEventRecord(t2, g.stream);
-        if (hipEventSynchronize(t2) != hipSuccess) return RSPT_E_HIP;
-        float ms_plain = 0.0f, ms_q = 0.0f;
-        (void)hipEventElapsedTime(&ms_plain, t0, t1);
-        (void)hipEventElapsedTime(&ms_q, t1, t2);
-        s->any_q_choice = ms_q < ms_plain ? 1 : 0;
-        if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: shadow rays of this scene: k_trace_w4<any> %.2f ms, k_trace_w4q %.2f ms on the same launch -> %s\n", ms_plain, ms_q, s->any_q_choice ? "the quantised records" : "the plain records");
-        return 1;
-    };
-    auto batch_volpath = [&](const Batch& bt, uint32_t& it) -> int {  // VolPathIntegrator::li (vol.h): the continuation queue doubles as the list of live paths
-        const uint32_t dgrid = grid_for(4);
-        const uint32_t null_passes = (uint32_t)env_size("RSPT_NULL_PASSES", 1024);
-        // LDS table: 10 dimensions per counted pass, 2 per pass through a medium boundary (room for 64 of those), 8 of read-ahead;
-        // a path that needs more is cut and counted (rspt_stats.truncated_paths); the reference's own limit is 1024
-        const uint32_t vnd = std::min(1024u, 5u + 10u * (d->max_depth + 2u) + 128u) + 8u;
-        if ((size_t)vnd * sob_bits * 4 > 64 * 1024) return fail(RSPT_E_UNSUPPORTED, "volpath: max_depth %u x %u index bits exceed the LDS Sobol' table", d->max_depth, sob_bits);
-        const uint32_t vlimit = halton ? vol_dim_limit : std::min(1024u, vnd - 8u);
-        hipLaunchKernelGGL(k_vol_init, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, g.vol, bt.n);
-        // counters: g.cnt[0 / 1] = the continuation queue of this / the next pass, g.cnt[2 / 3] = the shadow-ray segments
-        uint32_t live = bt.n;
-        for (uint32_t pass = 0; live > 0; pass++) {
-            const int par = pass & 1;
-            QueueCounts* cur = &g.cnt[par];
-            QueueCounts* nxt = &g.cnt[par ^ 1];
-            HIP_TRY(hipMemsetAsync(nxt, 0, sizeof(QueueCounts), g.stream));
-            HIP_TRY(hipMemsetAsync(&g.cnt[2], 0, sizeof(QueueCounts), g.stream));
-            ev_open(0, 0);
-            launch_trace<false, 0>(0, counters, tgrid, s, g.q[par][1], &cur->closest, 0, &cur->cursor_closest, g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
-            ev_close(0, 0);
-            trace_launches++;
-            vol_rays += live;
-            ev_open(2, 0);
-            if (s->has_textures) hipLaunchKernelGGL(k_texture, dim3(dgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, g.pb, g.q[par][1], &cur->closest, (const uint32_t*)nullptr, (const BinInfo*)nullptr);
-            if (ld.lazy) HIP_TRY(hipMemsetAsync(&cur->active, 0, sizeof(uint32_t), g.stream));   // (k_raygen leaves the batch size there; volpath itself does not use the active queues)
-            hipLaunchKernelGGL(s->has_dynamic ? k_vol_shade<true> : k_vol_shade<false>, dim3(dgrid), dim3(256), halton ? 0 : vnd * sob_bits * sizeof(uint32_t), g.stream, s->dev, ld, rd, g.pb, g.vol, g.q[par][1], &cur->closest,
-                               g.q[par ^ 1][1], &nxt->closest, g.q[0][2], &g.cnt[2].closest, vlimit, vnd, sob_bits, ld.lazy ? g.q[par][0] : (uint32_t*)nullptr, &cur->active);
-            // on-demand light voxels: paths whose voxel had no row were put back (q[par][0], counted in cur->active, zero until here); build the rows, run those paths
-            for (uint32_t round = 0; ld.lazy; round++) {
-                uint32_t claimed = 0;
-                if ((rc = build_claimed_rows(&claimed))) return rc;
-                HIP_TRY(hipMemcpyAsync(g.look, cur, sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-                const uint32_t n_retry = g.look[0].active;
-                if (n_retry == 0) break;
-                if (round > 64) return fail(RSPT_E_UNSUPPORTED, "volpath: on-demand light voxels did not settle in 64 rounds (not a device fault: the caller keeps its CPU loop, or asks for the eager table)");
-                // the retry queue becomes the input (copied to the other parity's active queue, which volpath does not use either), its counter starts again
-                HIP_TRY(hipMemcpyAsync(g.q[par ^ 1][0], g.q[par][0], (size_t)n_retry * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));
-                HIP_TRY(hipMemcpyAsync(&cur->any, &cur->active, sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));   // (cur->any: the retry run's input length)
-                HIP_TRY(hipMemsetAsync(&cur->active, 0, sizeof(uint32_t), g.stream));
-                hipLaunchKernelGGL(s->has_dynamic ? k_vol_shade<true> : k_vol_shade<false>, dim3(dgrid), dim3(256), halton ? 0 : vnd * sob_bits * sizeof(uint32_t), g.stream, s->dev, ld, rd, g.pb, g.vol,
-                                   g.q[par ^ 1][0], &cur->any, g.q[par ^ 1][1], &nxt->closest, g.q[0][2], &g.cnt[2].closest, vlimit, vnd, sob_bits, g.q[par][0], &cur->active);
-            }
-            ev_close(2, 0);
-            // VisibilityTester::tr: segments until every shadow ray has arrived or is blocked
-            // (the first two segments are launched without looking at the queue: most shadow rays cross at most one boundary, an
-            //  empty launch costs microseconds, a look costs a stream synchronisation; the look that follows also brings the
-            //  next pass's path count)
-            QueueCounts* look = g.look;   // (pinned: see Ctx::look)
-            bool have_live = false;
-            for (uint32_t seg = 0;; seg++) {
-                QueueCounts* tc = &g.cnt[2 + (seg & 1u)];
-                QueueCounts* tn = &g.cnt[2 + ((seg + 1u) & 1u)];
-                QueueCounts c{};
-                c.closest = live;   // upper bound while not looking (every live path has at most one shadow ray)
-                const bool looked = seg >= 2 || counters;   // (the counting pass wants every queue length)
-                if (looked) {
-                    HIP_TRY(hipMemcpyAsync(look, g.cnt, 4 * sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                    HIP_TRY(hipStreamSynchronize(g.stream));
-                    c = look[2 + (seg & 1u)];
-                    have_live = true;
-                    if (c.closest == 0) break;
-                }
-                if (seg > null_passes) { truncated += c.closest; break; }
-                HIP_TRY(hipMemsetAsync(tn, 0, sizeof(QueueCounts), g.stream));
-                ev_open(1, 0);
-                // (queue entries without the MIS flag over the shadow rays' own arrays, so that the hit's instance is recorded too)
-                g_inst_out = g.vol.hit_inst_tr ? g.hit_inst + g.cap : nullptr;
-                launch_trace<false, 0>(0, counters, tgrid, s, g.q[seg & 1u][2], &tc->closest, 0, &tc->cursor_closest, g.pb.ray_mis, g.pb.ray_mis, g.pb.hit_mis, g.pb.hit_mis, nullptr, nullptr, g.totals);
-                g_inst_out = nullptr;
-                ev_close(1, 0);
-                trace_launches++;
-                if (looked) vol_rays += c.closest;
-                hipLaunchKernelGGL(s->has_animated ? k_vol_tr<true> : k_vol_tr<false>, dim3(dgrid), dim3(256), 0, g.stream, s->dev, g.pb, g.vol, g.q[seg & 1u][2], &tc->closest, g.q[(seg + 1u) & 1u][2], &tn->closest);
-            }
-            if (!have_live) {
-                HIP_TRY(hipMemcpyAsync(look, g.cnt, 4 * sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-            }
-            live = look[par ^ 1].closest;
-            if (live && pass >= nominal_iters + null_passes) { truncated += live; break; }
-        }
-        it = 4;
-        return RSPT_OK;
-    };
-    auto batch_direct = [&](const Batch& bt, uint32_t& it) -> int {  // DirectLightingIntegrator::li (direct.h): specular tree, dimension assignment, light rounds, gather
-        const uint32_t nl = s->dev.n_lights, H = dl_H, md = d->max_depth;
-        const bool all = d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL;
-        const uint32_t n_arrays = (all && !whitted) ? 2u * md * nl : 0u;
-        // the sample arrays are filled for every pixel sample whether a node uses them or not (GlobalSampler::start_pixel), so they must fit;
-        // the regular stream behind them is checked per camera sample by k_dl_assign against what each tree really draws
-        const uint32_t dim_limit = halton ? vol_dim_limit + 1u : 1024u;
-        if (5ull + 2ull * n_arrays > dim_limit)
-            return fail(RSPT_E_UNSUPPORTED, "%s: %u sample arrays exceed the sampler's %u dimensions", dl_name, n_arrays, dim_limit);
-        DlBuf dl = g.dl;
-        dl.H = H; dl.levels = dl_levels;
-        s->dev.time_div = H;   // node h of camera sample s lives in slot s * H + h: its rays carry the sample's time (moving instances); estimate rays: below
-        struct TimeDivReset { rspt_scene_s* s; ~TimeDivReset() { s->dev.time_div = 1u; } } time_div_reset{s};
-        const size_t n_slots = (size_t)bt.n * H;
-        // virtual slots of the estimates (direct.h DlBuf::vs / vr): planes of n_slots, unless a moving instance needs slot -> camera sample by one division (RSPT_DL_PLANES=0: A/B)
-        const bool dl_planes = !s->has_animated && env_size("RSPT_DL_PLANES", 1) != 0;
-        dl.vs = dl_planes ? 1u : dl_R; dl.vr = dl_planes ? (uint32_t)n_slots : 1u;
-        if (s->has_textures) HIP_TRY(hipMemsetAsync(g.pb.state, 0, n_slots * sizeof(uint32_t), g.stream));   // (ST_NO_DIFF marks of k_dl_hit, read by k_dl_texture)
-        HIP_TRY(hipMemsetAsync(dl.le_kind, 0, n_slots * sizeof(float4), g.stream));
-        HIP_TRY(hipMemsetAsync(dl.l_all, 0, n_slots * sizeof(float4), g.stream));
-        HIP_TRY(hipMemsetAsync(dl.ld_acc, 0, n_slots * sizeof(float4), g.stream));
-        HIP_TRY(hipMemsetAsync(dl.error, 0, sizeof(uint32_t), g.stream));
-        // the camera rays were left in ray_cont[sample]; node slots overlay that array, so move them aside first
-        HIP_TRY(hipMemcpyAsync(g.pb.ray_sh, g.pb.ray_cont, (size_t)bt.n * sizeof(rspt_ray), hipMemcpyDeviceToDevice, g.stream));
-        // counters: g.cnt[level].closest = nodes of the level, .any = re-trace queue; rounds use g.cnt[md + 1 ..]
-        auto level_q = [&](uint32_t l) { return g.dl_queue + (size_t)bt.n * ((1u << l) - 1u); };
-        hipLaunchKernelGGL(k_dl_init, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, g.pb, dl, g.pb.ray_sh, level_q(0), &g.cnt[0].closest);
-        const uint32_t dgrid = grid_for(4);
-        for (uint32_t l = 0; l < dl_levels; l++) {
-            const uint32_t* queue = level_q(l);
-            const uint32_t* qcount = &g.cnt[l].closest;
-            for (uint32_t round = 0;; round++) {
-                QueueCounts* rc_ = &g.cnt[md + 1 + (round & 1u)];  // re-trace queue of this round (null-BSDF hits), double buffered
-                HIP_TRY(hipMemsetAsync(rc_, 0, sizeof(QueueCounts), g.stream));
-                HIP_TRY(hipMemsetAsync((void*)&g.cnt[l].cursor_closest, 0, 3 * sizeof(uint32_t), g.stream));
-                ev_open(0, 0);
-                launch_trace<false, 0>(0, false, tgrid, s, queue, qcount, 0, round == 0 ? &g.cnt[l].cursor_closest : &g.cnt[md + 1 + ((round - 1) & 1u)].cursor_closest,
-                                       g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
-                ev_close(0, 0);
-                trace_launches++;
-                ev_open(2, 0);
-                hipLaunchKernelGGL(k_dl_hit, dim3(dgrid), dim3(256), 0, g.stream, s->dev, rd, g.pb, dl, queue, qcount, g.q[round & 1u][0], &rc_->closest,
-                                   level_q(l + 1 < dl_levels ? l + 1 : l), &g.cnt[l + 1].closest, l);
-                ev_close(2, 0);
-                if (!s->has_null_material) break;
-                HIP_TRY(hipMemcpyAsync(g.look, rc_, sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-                const QueueCounts c = g.look[0];
-                if (c.closest == 0) break;
-                if (round >= env_size("RSPT_NULL_PASSES", 1024)) { truncated += c.closest; break; }
-                queue = g.q[round & 1u][0];
-                qcount = &rc_->closest;
-            }
-        }
-        hipLaunchKernelGGL(whitted ? k_dl_assign<true> : k_dl_assign<false>, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, dl, nl, n_arrays, all ? 1u : 0u, md, dim_limit);
-        if (s->has_textures)   // (dl_tex_wave: one level, the roots) the texture stage in front of the estimates
-            for (uint32_t l = 0; l < dl_levels; l++)
-                hipLaunchKernelGGL(k_dl_texture, dim3(dgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, g.pb, dl, level_q(l), &g.cnt[l].closest);
-        if (nl && dl_one_round) {   // every estimate of a level's nodes in one round: 4 launches per level (direct.h k_dl_nee_all)
-            QueueCounts* rc_ = &g.cnt[md + 3];
-            for (uint32_t l = 0; l < dl_levels; l++) {
-                HIP_TRY(hipMemsetAsync(rc_, 0, sizeof(QueueCounts), g.stream));
-                ev_open(2, 0);
-                // the estimate kernel per feature set, as k_shade<F>: scenes of Lambert / microfacet-reflection lobes under area lights without instances (C1 - C3) take the
-                // narrow build (RSPT_DL_VARIANT=generic forces the other)
-                constexpr uint32_t DLV_PLASTIC = SV_PLASTIC | SF_SOBOL | SF_HALTON;
-                const bool dl_narrow = (s->shade_features & ~DLV_PLASTIC) == 0 && !(getenv("RSPT_DL_VARIANT") && !strcmp(getenv("RSPT_DL_VARIANT"), "generic"));
-                const size_t dl_waves = env_size("RSPT_DL_WAVES", RSPT_DL_WAVES_DEFAULT);   // 3: the narrow build forced to 3 waves per SIMD
-                // the Sobol' tables the estimates read, in LDS (direct.h DlSob): the sample arrays' dimensions 5 .. 5 + 2 n_arrays and what the regular stream adds behind them,
-                // for indices of 2 log2_res + log2(spp x the longest array) bits; cut to 40 KB (the rest falls back to the global walks); RSPT_DL_LDS_SOBOL=0: as before
-                uint32_t dsn = 0, dsb = 0;
-                if (!halton && env_size("RSPT_DL_LDS_SOBOL", 1) != 0) {
-                    uint64_t longest = 1;
-                    for (uint32_t j = 0; all && d->n_light_samples && j < nl; j++) longest = std::max<uint64_t>(longest, (uint64_t)std::max<int32_t>(d->n_light_samples[j], 1));
-                    dsb = 2u * (uint32_t)rd.log2_res + 1u;
-                    for (uint64_t v = (uint64_t)std::max<int64_t>(d->spp, 1) * longest; v > 1; v >>= 1) dsb++;
-                    dsb = std::min(52u, dsb);
-                    dsn = std::min<uint32_t>(1024u, 5u + 2u * n_arrays + 8u * (md + 2u));
-                    if (whitted) dsn = (uint32_t)std::min<uint64_t>(1024u, 5u + (2ull * nl + 4u) * ((1ull << dl_levels) - 1u));   // the deepest tree's stream
-                    dsn = std::min<uint32_t>(dsn, (40u * 1024u) / (4u * dsb));
-                    if (dsn < 16u) dsn = dsb = 0;
-                }
-                // the lights and the area lights' triangle records in LDS too (direct.h DlSob::lights: their loads must not queue behind the estimates' stores); the count
-                // rides in bits 16.. of the index-bits argument.  RSPT_DL_LDS_LIGHTS=0: from global memory as before
-                const uint32_t dll = (nl <= DL_LDS_LIGHTS && env_size("RSPT_DL_LDS_LIGHTS", 1) != 0) ? nl : 0u;
-                const size_t dl_lds = (dll ? (((size_t)dll * (48 + sizeof(rspt_light)) + 7) / 8) * 8 : 0) + (dsn ? 104 * sizeof(uint64_t) + (size_t)dsn * dsb * sizeof(uint32_t) : 0);
-                dsb |= dll << 16;
-                if (whitted)   // (WhittedIntegrator: one estimate per light, direct.h dl_nee_all<F, true>)
-                    hipLaunchKernelGGL(dl_narrow ? k_wh_nee_all<DLV_PLASTIC> : k_wh_nee_all<SF_ALL>, dim3(dgrid), dim3(256), dl_lds, g.stream, s->dev, rd, bt, g.pb, dl, g.pix_list, level_q(l), &g.cnt[l].closest,
-                                       (const int32_t*)nullptr, dl_R, 0u, 1u, g.q[0][2], &rc_->any, g.q[0][1], &rc_->closest, dsn, dsb, dim_limit);
-                else
-                hipLaunchKernelGGL(dl_narrow ? (dl_waves == 3 ? k_dl_nee_all_w<DLV_PLASTIC, 3> : k_dl_nee_all<DLV_PLASTIC>) : k_dl_nee_all<SF_ALL>, dim3(dgrid), dim3(256), dl_lds, g.stream, s->dev, rd, bt, g.pb, dl, g.pix_list, level_q(l), &g.cnt[l].closest, (const int32_t*)dl_nls, dl_R,
-                                   n_arrays, all ? 1u : 0u, g.q[0][2], &rc_->any, g.q[0][1], &rc_->closest, dsn, dsb);
-                ev_close(2, 0);
-                ev_open(1, 0);
-                s->dev.time_div = H * dl_R;   // estimate r of node slot n sits in virtual slot n * R + r
-                {
-                    const int tuned = tune_any(bt.n, g.q[0][2], &rc_->any, &rc_->cursor_any, g.pb.ray_sh, g.pb.occluded, nullptr);   // (the scene's first large shadow-ray launch measures the two kernels)
-                    if (tuned < 0) return fail(tuned, "the shadow-ray kernel measurement failed");
-                    if (!tuned) launch_trace<true, 0>(0, false, tgrid, s, g.q[0][2], &rc_->any, 0, &rc_->cursor_any, g.pb.ray_sh, g.pb.ray_sh, nullptr, nullptr, g.pb.occluded, nullptr, g.totals);
-                }
-                ev_close(1, 0);
-                ev_open(0, 0);
-                launch_trace<false, 0>(0, false, tgrid, s, g.q[0][1], &rc_->closest, 0, &rc_->cursor_closest, g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
-                s->dev.time_div = H;
-                ev_close(0, 0);
-                trace_launches += 2;
-                hipLaunchKernelGGL(k_dl_nee_resolve_all, dim3(dgrid), dim3(256), 0, g.stream, s->dev, g.pb, dl, level_q(l), &g.cnt[l].closest, (const int32_t*)dl_nls, dl_R, n_arrays, all ? 1u : 0u);
-            }
-        } else if (nl) {
-            QueueCounts* rc_ = &g.cnt[md + 3];
-            for (uint32_t l = 0; l < dl_levels; l++) {
-                const uint32_t n_lights_round = all ? nl : 1u;
-                for (uint32_t j = 0; j < n_lights_round; j++) {
-                    const uint32_t n_j = all ? (uint32_t)(d->n_light_samples ? d->n_light_samples[j] : 1) : 1u;
-                    for (uint32_t kk = 0; kk < n_j; kk++) {
-                        HIP_TRY(hipMemsetAsync(rc_, 0, sizeof(QueueCounts), g.stream));
-                        ev_open(2, 0);
-                        hipLaunchKernelGGL(k_dl_nee, dim3(dgrid), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, dl, g.pix_list, level_q(l), &g.cnt[l].closest, j, kk, n_j,
-                                           n_arrays, all ? 1u : 0u, g.q[0][2], &rc_->any, g.q[0][1], &rc_->closest);
-                        ev_close(2, 0);
-                        ev_open(1, 0);
-                        launch_trace<true, 0>(0, false, tgrid, s, g.q[0][2], &rc_->any, 0, &rc_->cursor_any, g.pb.ray_sh, g.pb.ray_sh, nullptr, nullptr, g.pb.occluded, nullptr, g.totals);
-                        ev_close(1, 0);
-                        ev_open(0, 0);
-                        launch_trace<false, 0>(0, false, tgrid, s, g.q[0][1], &rc_->closest, 0, &rc_->cursor_closest, g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
-                        ev_close(0, 0);
-                        trace_launches += 2;
-                        hipLaunchKernelGGL(k_dl_nee_resolve, dim3(dgrid), dim3(256), 0, g.stream, s->dev, g.pb, dl, level_q(l), &g.cnt[l].closest, j, kk, n_j, n_arrays, all ? 1u : 0u);
-                    }
-                }
-            }
-        }
-        hipLaunchKernelGGL(k_dl_gather, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, g.pb, dl, nl, md);
-        uint32_t dl_err = 0;
-        HIP_TRY(hipMemcpyAsync(&dl_err, dl.error, sizeof dl_err, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        if (dl_err == 1u) return RSPT_DL_RETRY_LANE;   // a material with several specular lobes of one kind: the lobe choice depends on a sample value, the tree cannot be traced ahead
-        if (dl_err == 3u) return fail(RSPT_E_HIP, "%s: a specular bounce in a scene classified as having none", dl_name);
-        if (dl_err) return fail(RSPT_E_UNSUPPORTED, "%s: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dl_name, dim_limit);
-        it = md + 4;
-        return RSPT_OK;
-    };
-    auto batch_direct_lane = [&](const Batch& bt, uint32_t& it) -> int {  // the same integrator, one lane per camera sample (lane_serial.h)
-        const uint32_t nl = s->dev.n_lights, md = d->max_depth;
-        const bool all = d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL;
-        const uint32_t n_arrays = (all && !whitted) ? 2u * md * nl : 0u;
-        const uint32_t dim_limit = halton ? vol_dim_limit + 1u : 1024u;
-        if (5ull + 2ull * n_arrays > dim_limit)
-            return fail(RSPT_E_UNSUPPORTED, "%s: %u sample arrays exceed the sampler's %u dimensions", dl_name, n_arrays, dim_limit);
-        HIP_TRY(hipMemsetAsync(dl_words, 0, 2 * sizeof(uint32_t), g.stream));
-        const LaneDesc ln{all ? dl_nls : nullptr, n_arrays, all ? 1u : 0u, dim_limit, dl_tex, (uint32_t)dl_lanes, dl_tex_rows, dl_dyn,
-                          s->has_null_material ? (uint32_t)env_size("RSPT_NULL_PASSES", 1024) : 0u, dl_words, dl_words + 1};
-        const dim3 lgrid((bt.n + 63u) / 64u);
-        ev_open(2, 0);
-#define RSPT_LN(I, A) hipLaunchKernelGGL((k_lane_dl<I, A>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln)
-#define RSPT_LNW(I, A, M) hipLaunchKernelGGL((k_lane_dl<I, A, M, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln)
-        if (whitted) {   // WhittedIntegrator::li (lane_serial.h k_lane_dl<.., WH>)
-            if (s->has_animated) { if (s->has_alpha) RSPT_LNW(true, true, true); else RSPT_LNW(true, false, true); }
-            else if (s->has_instances) { if (s->has_alpha) RSPT_LNW(true, true, false); else RSPT_LNW(true, false, false); }
-            else { if (s->has_alpha) RSPT_LNW(false, true, false); else RSPT_LNW(false, false, false); }
-        } else if (s->has_animated) {   // (round 6: the walk interpolates the instances it enters at the sample's ray time, pb.time)
-            if (s->has_alpha) hipLaunchKernelGGL((k_lane_dl<true, true, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln);
-            else hipLaunchKernelGGL((k_lane_dl<true, false, true>), lgrid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, bt, g.pb, g.pix_list, ln);
-        } else if (s->has_instances) { if (s->has_alpha) RSPT_LN(true, true); else RSPT_LN(true, false); }
-        else { if (s->has_alpha) RSPT_LN(false, true); else RSPT_LN(false, false); }
-#undef RSPT_LNW
-#undef RSPT_LN
-        ev_close(2, 0);
-        uint32_t w[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(w, dl_words, sizeof w, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        if (w[0]) return fail(RSPT_E_UNSUPPORTED, "%s: a camera sample draws more than the sampler's %u dimensions (the reference panics there, sobol.rs:119-124)", dl_name, dim_limit);
-        truncated += w[1];
-        it = 1;
-        return RSPT_OK;
-    };
-    auto batch_ao = [&](const Batch& bt, uint32_t& it) -> int {  // AOIntegrator::li: closest hit, n shadow rays per hit, sum of the unoccluded terms
-        hipEvent_t e0 = get_event(n_ev++), e1 = get_event(n_ev++), e2 = get_event(n_ev++), e3 = get_event(n_ev++);
-        HIP_TRY(hipEventRecord(e0, g.stream));
-        ev_open(0, 0);
-        launch_trace<false, 0>(0, counters, tgrid, s, g.q[0][1], &g.cnt[0].closest, 0, &g.cnt[0].cursor_closest, g.pb.ray_cont, g.pb.ray_mis, g.pb.hit_cont, g.pb.hit_mis, nullptr, nullptr, g.totals);
-        ev_close(0, 0);
-        HIP_TRY(hipEventRecord(e1, g.stream));
-        hipLaunchKernelGGL(s->has_spheres ? k_ao_spawn_sph : (s->has_animated ? k_ao_spawn<true> : k_ao_spawn<false>), dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, g.pix_list, ao_n, d->ao_cos_sample, g.q[0][2], &g.cnt[1]);
-        HIP_TRY(hipEventRecord(e2, g.stream));
-        ev_open(1, 0);
-        s->dev.time_div = ao_n;   // shadow ray k of camera sample i sits in slot i * n + k: its Ray.time is the sample's (moving instances)
-        launch_trace<true, 0>(0, counters, tgrid, s, g.q[0][2], &g.cnt[1].any, 0, &g.cnt[1].cursor_any, g.pb.ray_sh, g.pb.ray_sh, nullptr, nullptr, g.pb.occluded, nullptr, g.totals);
-        s->dev.time_div = 1u;
-        ev_close(1, 0);
-        HIP_TRY(hipEventRecord(e3, g.stream));
-        trace_ev.push_back({e0, e1}); trace_ev.push_back({e2, e3});
-        trace_launches += 2;
-        hipLaunchKernelGGL(k_ao_resolve, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, bt, g.pb, ao_n);
-        it = 2;
-        return RSPT_OK;
-    };
-    auto batch_path = [&](const Batch& bt, uint32_t& it) -> int {  // PathIntegrator::li: trace (closest || any) -> [light voxels] -> [bins] -> [textures] -> shade, per bounce
-        for (;;) {
-            const int par = it & 1;
-            if (it > 0) g.pb.fresh = 0u;   // (PathBuf travels by value: the first launches of the batch have carried the flag k_raygen ran with)
-            const PathBuf P = move ? move_pathbuf(it, move_first) : g.pb;   // MOVE: the set this iteration reads (written by the previous one's shade launch) and the set it writes
-            hipEvent_t e0 = get_event(n_ev++), e1 = get_event(n_ev++);
-            HIP_TRY(hipEventRecord(e0, g.stream));
-            // the shadow-ray launch does not depend on the closest-hit launch: on a second stream its tail (a few
-            // long rays on an otherwise idle chip) overlaps the other launch
-            int any_lane = (it > 0 && two_streams) ? 1 : 0;
-            bool any_done = false;
-            if (it == 1) {   // (the scene's first large shadow-ray launch measures the two kernels: tune_any above)
-                ev_open(1, 0);
-                const int tuned = tune_any(bt.n, g.q[par][2], &g.cnt[it].any, &g.cnt[it].cursor_any, P.ray_sh, P.occluded, g.cnt[it].xcd_any);
-                ev_close(1, 0);
-                if (tuned < 0) return fail(tuned, "the shadow-ray kernel measurement failed");
-                if (tuned) { any_done = true; any_lane = 0; }
-            }
-            if (any_lane) {
-                HIP_TRY(hipEventRecord(ev_fork, g.stream));
-                HIP_TRY(hipStreamWaitEvent(g.stream2, ev_fork, 0));
-                ev_open(1, 1);
-                launch_trace<true, 0>(1, counters, tgrid, s, g.q[par][2], &g.cnt[it].any, 0, &g.cnt[it].cursor_any, P.ray_sh, P.ray_sh, nullptr, nullptr, P.occluded, nullptr, g.totals, g.cnt[it].xcd_any);
-                ev_close(1, 1);
-                HIP_TRY(hipEventRecord(ev_join, g.stream2));
-            }
-            ev_open(0, 0);
-            g_camera_launch = it == 0;
-            launch_trace<false, 0>(0, counters, tgrid, s, g.q[par][1], &g.cnt[it].closest, 0, &g.cnt[it].cursor_closest, P.ray_cont, P.ray_mis, P.hit_cont, P.hit_mis, nullptr, nullptr, g.totals, g.cnt[it].xcd_closest);
-            g_camera_launch = false;
-            ev_close(0, 0);
-            if (any_lane) HIP_TRY(hipStreamWaitEvent(g.stream, ev_join, 0));
-            else if (it > 0 && !any_done) {
-                ev_open(1, 0);
-                launch_trace<true, 0>(0, counters, tgrid, s, g.q[par][2], &g.cnt[it].any, 0, &g.cnt[it].cursor_any, P.ray_sh, P.ray_sh, nullptr, nullptr, P.occluded, nullptr, g.totals, g.cnt[it].xcd_any);
-                ev_close(1, 0);
-            }
-            HIP_TRY(hipEventRecord(e1, g.stream));
-            trace_ev.push_back({e0, e1});
-            trace_launches += it > 0 ? 2 : 1;
-            ev_open(2, 0);
-            const bool bins_now = shade_bins && (it > 0 || bins_first);
-            if (bins_now) {  // K7b: whole waves of one class for k_shade
-                const uint32_t bgrid = hinted_grid(grid_for(4), 256);
-                hipLaunchKernelGGL(k_bin_count, dim3(bgrid), dim3(256), 0, g.stream, s->dev, P, d->max_depth, g.q[par][0], &g.cnt[it], g.bin_keys, &g.bin_info[it]);
-                hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(64), 0, g.stream, &g.bin_info[it], g.q_sorted);
-                hipLaunchKernelGGL(k_bin_scatter, dim3(bgrid), dim3(256), 0, g.stream, g.q[par][0], &g.cnt[it], g.bin_keys, &g.bin_info[it], g.q_sorted);
-            }
-            if (ld_lazy && d->integrator == RSPT_INTEGRATOR_PATH) {
-                const uint32_t lgrid = hinted_grid(grid_for(4), 256);
-                hipLaunchKernelGGL(k_ld_mark, dim3(lgrid), dim3(256), 0, g.stream, s->dev, ld, P, d->max_depth, g.q[par][0], &g.cnt[it], ld_lazy->lazy, ld_lazy->new_list);
-                hipLaunchKernelGGL(k_ld_contrib_list, dim3(lgrid), dim3(256), 0, g.stream, s->dev, ld.nvox[0], ld.nvox[1], ld.nvox[2], ld_lazy->lazy, ld_lazy->new_list, ld_lazy->func);
-                hipLaunchKernelGGL(k_ld_build_list, dim3(lgrid), dim3(256), 0, g.stream, s->dev.n_lights, ld_lazy->lazy, ld_lazy->new_list, ld_lazy->func, ld_lazy->cdf, ld_lazy->func_int, ld_lazy->table);
-                hipLaunchKernelGGL(k_ld_commit, dim3(1), dim3(1), 0, g.stream, ld_lazy->lazy);
-            }
-            if (s->has_textures) {
-                const bool tex_sorted = bins_now && env_size("RSPT_TEXTURE_SORTED", 1) != 0;
-                hipLaunchKernelGGL(s->has_spheres ? k_texture_sph : k_texture, dim3(sgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, P, g.q[par][0], &g.cnt[it].active,
-                                   tex_sorted ? g.q_sorted : (const uint32_t*)nullptr, tex_sorted ? &g.bin_info[it] : (const BinInfo*)nullptr);
-            }
-            hipLaunchKernelGGL((move && it >= move_first) ? shade_move_k : shade_k, dim3(hinted_grid(sgrid, 256)), dim3(256), sob_nd * sob_bits * sizeof(uint32_t), g.stream, s->dev, ld, rd, P, g.q[par][0], &g.cnt[it], &g.cnt[it + 1], g.q[par ^ 1][0],
-                               g.q[par ^ 1][1], g.q[par ^ 1][2], counters ? g.totals + 2 : nullptr, sob_nd, sob_bits, (uint32_t)g.cap,
-                               bins_now ? g.q_sorted : (const uint32_t*)nullptr, bins_now ? &g.bin_info[it] : (const BinInfo*)nullptr);
-            ev_close(2, 0);
-            it++;
-            if (it < nominal_iters) continue;
-            // after max_depth + 1 bounces only pending estimates and null-material passes remain
-            if (max_iters == nominal_iters) break;
-            if (((it - nominal_iters) & 7u) != 0 && it < max_iters) continue;  // look at the queue length every 8th iteration: an empty iteration costs three idle launches, a look costs a stream sync
-            HIP_TRY(hipMemcpyAsync(g.look, &g.cnt[it], sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            const QueueCounts c = g.look[0];
-            if (c.active == 0 && c.active_tail == 0) break;
-            g_queue_hint = c.active + c.active_tail;
-            if (it >= max_iters) {  // the reference's loop would still be running (path.rs:109-116 has no limit); these paths keep the radiance gathered so far
-                truncated += c.active + c.active_tail;
-                if (getenv("RSPT_VERBOSE") && c.active) {  // where the endless paths are: slot, film position and the ray in flight
-                    uint32_t slots[4];
-                    const uint32_t k = std::min(c.active, 4u);
-                    HIP_TRY(hipMemcpy(slots, g.q[it & 1][0], k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                    for (uint32_t j = 0; j < k; j++) {
-                        rspt_ray r; float2 pf; float4 hc;
-                        const PathBuf D = move ? move_pathbuf(it, move_first) : g.pb;   // (MOVE: queue entries are positions; the film position lives at the original slot)
-                        uint32_t og = slots[j];
-                        if (move && it > move_first) HIP_TRY(hipMemcpy(&og, D.orig + slots[j], sizeof og, hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(&r, D.ray_cont + slots[j], sizeof r, hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(&pf, D.p_film + og, sizeof pf, hipMemcpyDeviceToHost));
-                        HIP_TRY(hipMemcpy(&hc, D.hit_cont + slots[j], sizeof hc, hipMemcpyDeviceToHost));
-                        uint32_t o[3], dd[3], pr;
-                        memcpy(o, r.o, 12); memcpy(dd, r.d, 12); memcpy(&pr, &hc.x, 4);
-                        fprintf(stderr, "rspt: endless null-surface path: slot %u film (%.3f, %.3f) ray o %08x %08x %08x d %08x %08x %08x last prim %u\n",
-                                slots[j], pf.x, pf.y, o[0], o[1], o[2], dd[0], dd[1], dd[2], pr);
-                    }
-                }
-                break;
-            }
-        }
-        // MOVE: whatever is still queued (paths cut at max_iters; normally nothing) hands its radiance to the film's array
-        if (move) hipLaunchKernelGGL(k_move_flush, dim3(grid_for(1)), dim3(256), 0, g.stream, move_pathbuf(it, move_first), g.q[it & 1][0], &g.cnt[it], (uint32_t)g.cap, it > move_first ? 1u : 0u);
-        return RSPT_OK;
-    };
-    auto run_tile_serial = [&]() -> int {  // the pixel samplers: one lane per tile (tile_serial.h)
-
-        // ---- one lane per tile (tile_serial.h) ----
-        std::vector<TileRec> tiles;
-        for (size_t i = 0; i < blocks.size(); i++) {
-            if ((i / chunk) % shard_count != d->shard_index) continue;
-            const int32_t x0 = sb[0] + (int32_t)blocks[i].first * ts, x1 = std::min(x0 + ts, sb[2]);
-            const int32_t y0 = sb[1] + (int32_t)blocks[i].second * ts, y1 = std::min(y0 + ts, sb[3]);
-            tiles.push_back(TileRec{(int16_t)x0, (int16_t)y0, (int16_t)x1, (int16_t)y1, (uint32_t)((int32_t)blocks[i].second * ntx + (int32_t)blocks[i].first), 0u, 0u});
-        }
-        const uint32_t n_tiles = (uint32_t)tiles.size();
-        const uint32_t spp = (uint32_t)d->spp, nd = d->pixel_dimensions;
-        // rows of every tile per pass: as many as the sample-result arrays (24 B per sample) allow
-        const size_t samp_cap = std::max<size_t>(env_size("RSPT_SERIAL_SAMPLES", (size_t)1 << 28), (size_t)ts * spp);
-        int32_t rows = ts;
-        while (rows > 1 && (size_t)n_tiles * rows * ts * spp > samp_cap) rows--;
-        if ((size_t)n_tiles * rows * ts * spp > ((size_t)1 << 31)) return fail(RSPT_E_UNSUPPORTED, "pixel sampler: %u tiles x %u spp do not fit one pass", n_tiles, spp);
-        struct Guard { std::vector<void*> p; ~Guard() { for (void* q : p) (void)hipFree(q); } } guard;
-        auto tmp = [&](auto** p, size_t n) { int r = dev_alloc(p, std::max<size_t>(n, 1)); if (!r) guard.p.push_back(*p); return r; };
-        TileRec* tiles_d = nullptr; float4* samp_L = nullptr; float2* samp_pf = nullptr; float* a1 = nullptr; float2* a2 = nullptr; uint64_t* rng_state = nullptr; uint64_t* rng_saved = nullptr;
-        // the integrator's 2-D sample arrays (request_2d_array in preprocess): ao one of n_samples (ao.rs:47-49); directlighting, strategy all,
-        // two per light and recursion level (directlighting.rs:54-70)
-        float2* arr = nullptr; uint32_t* arr_sz_d = nullptr; uint32_t* arr_base_d = nullptr; int32_t* nls_d = nullptr;
-        std::vector<uint32_t> arr_sz;
-        if (ao) arr_sz.push_back(d->ao_n_samples);
-        if (direct && !whitted && d->direct_strategy == RSPT_DIRECT_SAMPLE_ALL)   // (whitted.rs requests no arrays)
-            for (uint32_t lvl = 0; lvl < d->max_depth; lvl++)
-                for (uint32_t j = 0; j < s->dev.n_lights; j++) { const uint32_t n = d->n_light_samples ? (uint32_t)d->n_light_samples[j] : 1u; arr_sz.push_back(n); arr_sz.push_back(n); }
-        std::vector<uint32_t> arr_base(arr_sz.size());
-        uint32_t arr_total = 0;
-        for (size_t a = 0; a < arr_sz.size(); a++) { arr_base[a] = arr_total * spp; arr_total += arr_sz[a]; }
-        if ((size_t)arr_total * spp * n_tiles > ((size_t)1 << 31)) return fail(RSPT_E_UNSUPPORTED, "pixel sampler: %u sample-array points x %u spp x %u tiles", arr_total, spp, n_tiles);
-        if (!arr_sz.empty()) {
-            if ((rc = tmp(&arr, (size_t)arr_total * spp * n_tiles)) || (rc = tmp(&arr_sz_d, arr_sz.size())) || (rc = tmp(&arr_base_d, arr_sz.size()))) return rc;
-            HIP_TRY(hipMemcpyAsync(arr_sz_d, arr_sz.data(), arr_sz.size() * 4, hipMemcpyHostToDevice, g.stream));
-            HIP_TRY(hipMemcpyAsync(arr_base_d, arr_base.data(), arr_base.size() * 4, hipMemcpyHostToDevice, g.stream));
-        }
-        if (direct && d->n_light_samples && s->dev.n_lights) {
-            if ((rc = tmp(&nls_d, s->dev.n_lights))) return rc;
-            HIP_TRY(hipMemcpyAsync(nls_d, d->n_light_samples, s->dev.n_lights * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));   // (the caller's array, and the vectors above, must outlive the copies)
-        }
-        uint32_t* c_pixel_d = nullptr; uint32_t* trunc_d = nullptr; uint32_t* pass_pix = nullptr;
-        const size_t max_samples = (size_t)n_tiles * rows * ts * spp;
-        if ((rc = tmp(&tiles_d, n_tiles)) || (rc = tmp(&samp_L, max_samples)) || (rc = tmp(&samp_pf, max_samples)) || (rc = tmp(&a1, (size_t)nd * spp * n_tiles)) ||
-            (rc = tmp(&a2, (size_t)nd * spp * n_tiles)) || (rc = tmp(&rng_state, 2 * (size_t)n_tiles)) || (rc = tmp(&rng_saved, ld.lazy ? 2 * (size_t)n_tiles : 1)) || (rc = tmp(&c_pixel_d, 32)) || (rc = tmp(&trunc_d, 2)) ||
-            (rc = tmp(&pass_pix, (size_t)n_tiles * rows * ts)))
-            return rc;
-        HIP_TRY(hipMemsetAsync(trunc_d, 0, sizeof(uint32_t), g.stream));
-        if (d->sampler_kind == RSPT_SAMPLER_MAXMINDIST) HIP_TRY(hipMemcpyAsync(c_pixel_d, d->maxmin_c_pixel, 32 * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
-        const PixDesc pd{d->sampler_kind, spp, d->sampler_kind == RSPT_SAMPLER_RANDOM ? 0u : nd, d->strat_x, d->strat_y, d->strat_jitter, c_pixel_d, a1, a2, rng_state, arr, arr_sz_d, arr_base_d, (uint32_t)arr_sz.size(), arr_total, d->ao_cos_sample, nls_d, d->direct_strategy, dl_tex, dl_tex_rows, dl_dyn};
-        // lanes per wave: a lane that shares its wave waits whenever the others diverge (measured: four lanes of a wave take four times one lane's
-        // time — no overlap at all), so the tiles are spread over waves, up to twice what the chip holds at these kernels' 2 waves / SIMD
-        // (256 CUs x 4 SIMDs x 2 = 2048) before doubling up: C3 frame, 8160 tiles, 02sequence — 2048: 21.9, 4096: 24.7, 8192: 21.7 Msamples/s;
-        // builds forced to 3 / 4 waves per SIMD (168 / 128 VGPRs, 2.3 / 2.5 KB of scratch) lose to the spills: 17.8 - 21.5
-        uint32_t lanes = 1;
-        while (lanes < 64 && (n_tiles + lanes - 1) / lanes > (uint32_t)env_size("RSPT_SERIAL_WAVES", 4096)) lanes *= 2;
-        if (s->has_dynamic && (rc = ensure_dyn_built(((n_tiles + lanes - 1) / lanes) * 64u))) return rc;   // one lobe record per thread of the launch
-        PathBuf fpb = g.pb;
-        fpb.L_eta = samp_L; fpb.p_film = samp_pf;
-        const uint32_t serial_iters = nominal_iters + 1u + (s->has_null_material ? (uint32_t)env_size("RSPT_NULL_PASSES", 1024) : 0u);
-        std::vector<uint32_t> pl;
-        for (int32_t r0 = 0; r0 < ts; r0 += rows) {
-            const int32_t r1 = std::min(r0 + rows, ts);
-            pl.clear();
-            for (TileRec& t : tiles) {
-                t.pix0 = (uint32_t)pl.size();
-                for (int32_t y = t.y0 + r0; y < t.y0 + r1 && y < t.y1; y++)
-                    for (int32_t x = t.x0; x < t.x1; x++) pl.push_back(((uint32_t)(uint16_t)(int16_t)y << 16) | (uint32_t)(uint16_t)(int16_t)x);
-            }
-            if (pl.empty()) continue;
-            HIP_TRY(hipStreamSynchronize(g.stream));  // the previous pass still reads tiles_d / pass_pix
-            HIP_TRY(hipMemcpyAsync(tiles_d, tiles.data(), n_tiles * sizeof(TileRec), hipMemcpyHostToDevice, g.stream));
-            HIP_TRY(hipMemcpyAsync(pass_pix, pl.data(), pl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
-            const dim3 grid((n_tiles + lanes - 1) / lanes);
-            // on-demand light voxels: a lane claims the voxels it finds without a row (dev_scene.h light_row_try) and goes on with row 0; the claimed rows are
-            // built and the rows of the tiles rendered again from the saved generator states, until a run claims nothing — only that run's samples are kept
-            // (a wrong row can change how many dimensions an estimate draws, so a run may leave the true paths after its first missing voxel: each
-            // round completes at least the first one along every true chain)
-            if (ld.lazy) {
-                HIP_TRY(hipMemcpyAsync(rng_saved, rng_state, 2 * (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToDevice, g.stream));
-                HIP_TRY(hipMemcpyAsync(trunc_d + 1, trunc_d, sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));
-            }
-            for (uint32_t lazy_round = 0;; lazy_round++) {
-            if (ld.lazy && lazy_round > 0) {
-                HIP_TRY(hipMemcpyAsync(rng_state, rng_saved, 2 * (size_t)n_tiles * sizeof(uint64_t), hipMemcpyDeviceToDevice, g.stream));
-                HIP_TRY(hipMemcpyAsync(trunc_d, trunc_d + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));
-            }
-            ev_open(2, 0);
-#define RSPT_TS(I, A, O) hipLaunchKernelGGL((k_tile_serial<I, A, O>), grid, dim3(64), 0, g.stream, s->dev, s->tex, ld, rd, g.pb, pd, tiles_d, n_tiles, lanes, r0, r1, samp_L, samp_pf, serial_iters, trunc_d)
-            if (s->has_animated) {   // (round 6: modes 5 - 8 = path / ao / volpath / directlighting with the instances' Transforms interpolated at the camera sample's time)
-                if (ao) { if (s->has_alpha) RSPT_TS(true, true, 6); else RSPT_TS(true, false, 6); }
-                else if (volpath) { if (s->has_alpha) RSPT_TS(true, true, 7); else RSPT_TS(true, false, 7); }
-                else if (whitted) { if (s->has_alpha) RSPT_TS(true, true, 10); else RSPT_TS(true, false, 10); }
-                else if (direct) { if (s->has_alpha) RSPT_TS(true, true, 8); else RSPT_TS(true, false, 8); }
-                else { if (s->has_alpha) RSPT_TS(true, true, 5); else RSPT_TS(true, false, 5); }
-            } else if (ao) {
-                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 1); else RSPT_TS(true, false, 1); }
-                else { if (s->has_alpha) RSPT_TS(false, true, 1); else RSPT_TS(false, false, 1); }
-            } else if (volpath) {
-                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 2); else RSPT_TS(true, false, 2); }
-                else { if (s->has_alpha) RSPT_TS(false, true, 2); else RSPT_TS(false, false, 2); }
-            } else if (whitted) {   // (modes 9 / 10: WhittedIntegrator::li, tile_serial.h)
-                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 9); else RSPT_TS(true, false, 9); }
-                else { if (s->has_alpha) RSPT_TS(false, true, 9); else RSPT_TS(false, false, 9); }
-            } else if (direct) {
-                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 3); else RSPT_TS(true, false, 3); }
-                else { if (s->has_alpha) RSPT_TS(false, true, 3); else RSPT_TS(false, false, 3); }
-            } else if (s->has_dynamic) {
-                if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 4); else RSPT_TS(true, false, 4); }
-                else { if (s->has_alpha) RSPT_TS(false, true, 4); else RSPT_TS(false, false, 4); }
-            } else if (s->has_instances) { if (s->has_alpha) RSPT_TS(true, true, 0); else RSPT_TS(true, false, 0); }
-            else { if (s->has_alpha) RSPT_TS(false, true, 0); else RSPT_TS(false, false, 0); }
-#undef RSPT_TS
-            ev_close(2, 0);
-            if (!ld.lazy) break;
-            uint32_t claimed = 0;
-            if ((rc = build_claimed_rows(&claimed))) return rc;
-            if (claimed == 0) break;
-            if (lazy_round > 64) return fail(RSPT_E_UNSUPPORTED, "pixel sampler: on-demand light voxels did not settle in 64 rounds (not a device fault: the caller keeps its CPU loop, or asks for the eager table)");
-            }
-            const uint32_t npx = (uint32_t)pl.size();
-            Batch bt{0u, npx, 0u, spp, npx * spp};
-            samples += bt.n;
-            if ((rc = film_index(pass_pix, npx))) return rc;
-            film_stage(rd, bt, fpb, pass_pix);
-        }
-        uint32_t tv = 0;
-        HIP_TRY(hipMemcpyAsync(&tv, trunc_d, sizeof tv, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        truncated += tv;
-        return RSPT_OK;
-    };
-    if (pixel_sampler) {
-        size_t my_tiles = 0;
-        for (size_t i = 0; i < blocks.size(); i++) my_tiles += (i / chunk) % shard_count == d->shard_index;
-        const size_t min_tiles = env_size("RSPT_SERIAL_MIN_TILES", 2048);   // (round 4, statue frame under 02sequence, GPU vs 256 host threads, Msamples/s: 920 tiles 5.6 / 8.9, 2040: 11.2 / 8.0, 4080: 19.3 / 7.8, 8160: 26.7 / 7.3)
-        if (!d->allow_slow_paths && my_tiles < min_tiles)
-            return fail(RSPT_E_UNSUPPORTED, "a pixel sampler over %zu tiles: one lane per tile is slower than the host's tile loop below ~%zu tiles (set allow_slow_paths to run it anyway)", my_tiles, min_tiles);
-    }
-    if (pixel_sampler && (rc = run_tile_serial())) return rc;
-    if (!pixel_sampler && (rc = film_index(g.pix_list, (uint32_t)n_pix))) return rc;
-    for (size_t p0 = 0; !pixel_sampler && p0 < n_pix; p0 += pix_per_batch) {
-        const uint32_t npx = (uint32_t)std::min(pix_per_batch, n_pix - p0);
-        for (uint32_t s0 = (uint32_t)smp_begin; s0 < (uint32_t)smp_end; s0 += ns) {
-            const uint32_t ns_b = std::min(ns, (uint32_t)smp_end - s0);  // Halton spp need not be a power of two
-            Batch bt{(uint32_t)p0, npx, s0, ns_b, npx * ns_b};
-            samples += bt.n;
-            HIP_TRY(hipMemsetAsync(g.cnt, 0, (size_t)g.n_cnt * sizeof(QueueCounts), g.stream));
-            if (shade_bins) HIP_TRY(hipMemsetAsync(g.bin_info, 0, (size_t)std::min<uint32_t>(g.n_bin_info, max_iters + 10) * sizeof(BinInfo), g.stream));
-            // the path integrator's first shade launch knows what k_raygen would have written into L_eta / beta (PathBuf::fresh); RSPT_FRESH=0: written and read as before
-            const bool fresh_ok = !volpath && !direct && !ao && env_size("RSPT_FRESH", 1) != 0;
-            g.pb.fresh = fresh_ok ? 1u : 0u;
-            hipLaunchKernelGGL(k_raygen, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, rd, bt, g.pb, g.pix_list, g.q[0][0], g.q[0][1], g.cnt);   // (MOVE or not: iteration 0 lives in set 0 = pb's own arrays, by slot)
-            uint32_t it = 0;
-            g_queue_hint = 0xffffffffu;
-            if (volpath) rc = batch_volpath(bt, it);
-            else if (direct) {
-                rc = dl_lane ? batch_direct_lane(bt, it) : batch_direct(bt, it);
-                if (rc == RSPT_DL_RETRY_LANE) {   // from here on the per-lane form serves this render; this batch starts over
-                    dl_lane = true;
-                    HIP_TRY(hipMemsetAsync(g.cnt, 0, (size_t)g.n_cnt * sizeof(QueueCounts), g.stream));
-                    g.pb.fresh = 0u;
-                    hipLaunchKernelGGL(k_raygen, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, rd, bt, g.pb, g.pix_list, g.q[0][0], g.q[0][1], g.cnt);
-                    rc = batch_direct_lane(bt, it);
-                }
-            }
-            else if (ao) rc = batch_ao(bt, it);
-            else rc = batch_path(bt, it);
-            if (rc) return rc;
-            if (getenv("RSPT_QUEUE_LOG") && p0 == 0 && s0 == (uint32_t)smp_begin) {   // the queue lengths of the render's first batch, per wavefront iteration (profiles/rNN_shade_ledger.md)
-                std::vector<QueueCounts> qc(it + 1);
-                HIP_TRY(hipMemcpyAsync(qc.data(), g.cnt, (it + 1) * sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-                for (uint32_t k = 0; k <= it; k++)
-                    fprintf(stderr, "rspt: queue it %u: active %u (+ %u that only wait for an estimate) closest %u any %u of %u paths\n", k, qc[k].active, qc[k].active_tail, qc[k].closest, qc[k].any, bt.n);
-            }
-            if (getenv("RSPT_QUEUE_LOG") && p0 == 0 && s0 == (uint32_t)smp_begin) {   // the queue lengths of the render's first batch, per wavefront iteration (profiles/rNN_shade_ledger.md)
-                std::vector<QueueCounts> qc(it + 1);
-                HIP_TRY(hipMemcpyAsync(qc.data(), g.cnt, (it + 1) * sizeof(QueueCounts), hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-                for (uint32_t k = 0; k <= it; k++)
-                    fprintf(stderr, "rspt: queue it %u: active %u (+ %u that only wait for an estimate) closest %u any %u of %u paths\n", k, qc[k].active, qc[k].active_tail, qc[k].closest, qc[k].any, bt.n);
-            }
-            if (counters) hipLaunchKernelGGL(k_accum_counts, dim3(1), dim3(1), 0, g.stream, g.cnt, it, g.totals);
-            film_stage(rd, bt, g.pb, g.pix_list);   // (MOVE: ended paths have written their radiance to pb.L_eta by original slot, move_pathbuf)
-        }
-    }
-    g_queue_hint = 0xffffffffu;
-    float4* out_dev = film_dev ? (float4*)film_dev : g.film_out;
-    hipLaunchKernelGGL(k_film_resolve, dim3((uint32_t)((film_px + 255) / 256)), dim3(256), 0, g.stream, g.film_own, g.film_splat, out_dev, (uint32_t)film_px);
-    if (d->film_reduce) {  // X1: sum of the ranks' films onto rank 0 (a sum, not a gather: tile pixel bounds overlap, film.rs:321-330)
-        if (!rc_.comm) return fail(RSPT_E_INVALID, "film_reduce without a communicator (rspt_comm_init)");
-        if ((uint32_t)rc_.world != shard_count || (uint32_t)rc_.rank != d->shard_index)
-            return fail(RSPT_E_INVALID, "film_reduce: shard %u of %u does not match rank %d of %d", d->shard_index, shard_count, rc_.rank, rc_.world);
-        hipError_t pe = hipStreamSynchronize(g.stream);   // a kernel fault of this rank must surface before the agreement, not inside the collective
-        if (pe != hipSuccess) return fail(RSPT_E_HIP, "render failed: %s", hipGetErrorString(pe));
-        int32_t any_failed = 0;
-        if (int rc = film_reduce_agree(0, &any_failed)) return rc;
-        if (any_failed) return fail(RSPT_E_PEER, "film_reduce: another rank of the communicator failed its render; no film was summed");
-        RCCL_TRY(rc_.Reduce(out_dev, out_dev, film_px * 4, ncclFloat32, ncclSum, 0, rc_.comm, g.stream));
-    }
-    HIP_TRY(hipEventRecord(ev_k1, g.stream));
-    HIP_TRY(hipGetLastError());
-    if (film_host) HIP_TRY(hipMemcpyAsync(film_host, out_dev, film_px * sizeof(float4), hipMemcpyDeviceToHost, g.stream));
-    if (li_host) HIP_TRY(hipMemcpyAsync(li_host, li_dev, film_px * (size_t)d->spp * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
-    hipError_t se = hipStreamSynchronize(g.stream);
-    if (se != hipSuccess) return fail(RSPT_E_HIP, "render failed: %s", hipGetErrorString(se));
-    if (ld_lazy) {
-        LightLazy lz;
-        HIP_TRY(hipMemcpy(&lz, ld_lazy->lazy, sizeof lz, hipMemcpyDeviceToHost));
-        if (lz.overflow) {
-            LightLazy reset{0u, lz.n_rows, lz.max_rows, 0u};
-            (void)hipMemcpy(ld_lazy->lazy, &reset, sizeof reset, hipMemcpyHostToDevice);
-            return fail(RSPT_E_NOMEM, "spatial light distribution: more than %u voxels were touched; raise RSPT_LIGHT_TABLE_POOL_BYTES", lz.max_rows);
-        }
-    }
-    auto t_end = std::chrono::steady_clock::now();
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->t_render_s = std::chrono::duration<double>(t_end - t_start).count();
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev_k0, ev_k1));
-        stats->t_kernels_s = ms * 1e-3;
-        double tr = 0;
-        for (auto& e : trace_ev) {
-            float m = 0;
-            if (hipEventElapsedTime(&m, e.first, e.second) == hipSuccess) tr += m;
-        }
-        stats->t_trace_s = tr * 1e-3;
-        double ksum[3] = {0, 0, 0};
-        for (int k = 0; k < 3; k++)
-            for (auto& e : kev[k]) {
-                float m = 0;
-                if (hipEventElapsedTime(&m, e.first, e.second) == hipSuccess) ksum[k] += m;
-            }
-        stats->t_trace_closest_s = ksum[0] * 1e-3; stats->t_trace_any_s = ksum[1] * 1e-3; stats->t_shade_s = ksum[2] * 1e-3;
-        stats->launches_closest = kev[0].size(); stats->launches_any = kev[1].size();
-        if (volpath) {  // paths vol.h cut because the sampler ran out of dimensions
-            uint32_t tv = 0;
-            HIP_TRY(hipMemcpy(&tv, g.vol.truncated, sizeof tv, hipMemcpyDeviceToHost));
-            truncated += tv;
-        }
-        stats->truncated_paths = truncated;
-        stats->samples = samples;
-        stats->trace_launches = trace_launches;
-        unsigned long long tot[8];
-        HIP_TRY(hipMemcpy(tot, g.totals, sizeof tot, hipMemcpyDeviceToHost));
-        stats->nan_samples = tot[5];
-        if (volpath) { tot[3] = vol_rays; tot[4] = 0; }  // every volpath ray is a closest-hit ray (shadow rays walk segment by segment); counted from the queue lengths the host reads
-        if (counters) {
-            stats->nodes_visited = tot[0]; stats->tris_tested = tot[1];
-            stats->rays_closest = tot[3]; stats->rays_any = tot[4];
-            // B_alg = sum(32 N_node + 48 N_tri) + 96 R_closest + 72 R_any + 96 N_bounce + 32 per sample
-            stats->alg_bytes = 32.0 * (double)tot[0] + 48.0 * (double)tot[1] + 96.0 * (double)tot[3] + 72.0 * (double)tot[4] + 96.0 * (double)tot[2] + 32.0 * (double)samples;
-        }
-    }
-    return RSPT_OK;
+    if ((rc = r.constants()) || (rc = r.shard_pixels()) || (rc = r.film_buffers(li_host)) || (rc = r.size_batches()) || (rc = r.prepare())) return rc;
+    if ((rc = r.run()) || (rc = r.finish(film_host, film_dev, li_host))) return rc;
+    return r.report(stats, t_start);
 }
 
 }  // namespace
@@ -3117,15 +1749,16 @@ int rspt_trace_device(rspt_scene_t s, const void* rays_dev, uint64_t n, void* ou
     if (counters) HIP_TRY(hipMemsetAsync(g.totals, 0, 8 * sizeof(unsigned long long), g.stream));
     hipEvent_t e0 = get_event(0), e1 = get_event(1);
     HIP_TRY(hipEventRecord(e0, g.stream));
-    int rc0 = ensure_counts(4);
-    if (!rc0) rc0 = ensure_overflow_list(std::max<size_t>((size_t)n, 1));
+    int rc0 = ensure_array(&g.cnt, &g.n_cnt, 4);
+    if (!rc0) rc0 = ensure_array(&g.ovf, &g.ovf_cap, std::max<size_t>((size_t)n, 1));
     if (!rc0) rc0 = ensure_spill(pw_spill_threads());
     if (rc0) return rc0;
-    uint32_t* cursor = &g.cnt[0].cursor_closest;
+    TraceCall c; c.count_imm = (uint32_t)n; c.cursor = &g.cnt[0].cursor_closest; c.ra = c.rb = (const rspt_ray*)rays_dev; c.hits = (rspt_hit*)out_dev;
+    c.count = counters; c.counters = g.totals; c.xcd_cursors = any_hit ? g.cnt[0].xcd_any : g.cnt[0].xcd_closest;
     for (int r = 0; r < repeat && n; r++) {
         HIP_TRY(hipMemsetAsync(&g.cnt[0], 0, sizeof(QueueCounts), g.stream));
-        if (any_hit) launch_trace<true, 1>(0, counters, trace_grid(), s, nullptr, nullptr, (uint32_t)n, cursor, (const rspt_ray*)rays_dev, (const rspt_ray*)rays_dev, nullptr, nullptr, nullptr, (rspt_hit*)out_dev, g.totals, g.cnt[0].xcd_any);
-        else launch_trace<false, 1>(0, counters, trace_grid(), s, nullptr, nullptr, (uint32_t)n, cursor, (const rspt_ray*)rays_dev, (const rspt_ray*)rays_dev, nullptr, nullptr, nullptr, (rspt_hit*)out_dev, g.totals, g.cnt[0].xcd_closest);
+        if (any_hit) launch_trace<true, 1>(trace_grid(), s, c);
+        else launch_trace<false, 1>(trace_grid(), s, c);
     }
     HIP_TRY(hipEventRecord(e1, g.stream));
     HIP_TRY(hipGetLastError());

@@ -107,7 +107,7 @@ template <typename F>
 RDEV bool vol_estimate(const SceneDev& sc, const LightDistDev& ld, const RenderDev& rd, const PathBuf& pb, const VolBuf& vb, uint32_t p, VolSampler& smp,
                        const VolRef& it, rgb beta, bool* retry, F&& scatter /* (wi, &pdf) -> f */) {
     // on-demand spatial distribution: a voxel without a row yet is claimed (light_row_try) and the path is put back, untouched, for the run
-    // that follows the build of the claimed rows (librspt.hip batch_volpath) — nothing of this pass has been written for it at this point
+    // that follows the build of the claimed rows (render_schedules.h batch_volpath) — nothing of this pass has been written for it at this point
     const int32_t row = light_row_try(ld, light_voxel(sc, ld, it.p));
     if (row < 0 && ld.lazy) { *retry = true; return false; }
     const uint32_t vox = row < 0 ? 0u : (uint32_t)row;
