@@ -40,7 +40,7 @@ struct RenderRun {
     uint64_t samples = 0, truncated = 0, vol_rays = 0, trace_launches = 0; uint32_t queue_hint = 0xffffffffu;
     int validate(), constants(), shard_pixels(), film_buffers(const float* li_host), size_batches(), prepare(), run(), run_tile_serial();
     int finish(float* film_host, void* film_dev, float* li_host), report(rspt_stats* stats, std::chrono::steady_clock::time_point t_start);
-    int film_index(const uint32_t* list, uint32_t n), build_claimed_rows(uint32_t* n_claimed), tune_any(uint32_t batch_n, TraceCall c);
+    int film_index(const uint32_t* list, uint32_t n), build_claimed_rows(uint32_t* n_claimed), tune_any(uint32_t batch_n, TraceCall c), tune_camera(uint32_t batch_n, TraceCall c);
     void film_stage(const RenderDev& rd_, const Batch& bt, const PathBuf& fpb, const uint32_t* list);
     int batch_volpath(const Batch& bt, uint32_t& it), batch_direct(const Batch& bt, uint32_t& it), batch_direct_lane(const Batch& bt, uint32_t& it);
     int batch_ao(const Batch& bt, uint32_t& it), batch_path(const Batch& bt, uint32_t& it);

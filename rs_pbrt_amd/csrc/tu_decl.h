@@ -7,6 +7,7 @@
 #include "lane_serial.h"
 #include "trace_w4.h"
 #include "trace_w4q.h"
+#include "trace_packet.h"
 
 namespace rspt {
 
@@ -167,6 +168,12 @@ RSPT_TU_SHADE_MW(SV_DIFFUSE_H, 3) RSPT_TU_SHADE_MW(SV_PLASTIC_H, 3)
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4Q)
 RSPT_TU_X template __global__ void k_trace_w4q<0>(SceneDev, const Quad4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, uint32_t*, rspt_hit*, uint32_t*, int, int, uint32_t, uint32_t, const float4*);
 RSPT_TU_X template __global__ void k_trace_w4q<1>(SceneDev, const Quad4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, uint32_t*, rspt_hit*, uint32_t*, int, int, uint32_t, uint32_t, const float4*);
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4PK)
+#define RSPT_TU_W4PK(OM) \
+    RSPT_TU_X template __global__ void k_trace_w4pk<OM>(SceneDev, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, \
+                                                        rspt_hit*, uint32_t, const float4*);
+RSPT_TU_W4PK(0) RSPT_TU_W4PK(1)   /* the packet walk of coherent closest-hit launches (trace_packet.h): the render's queues, the trace hook */
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4)
 RSPT_TU_W4_4(false, 0) RSPT_TU_W4_4(false, 1) RSPT_TU_W4_4(true, 0) RSPT_TU_W4_4(true, 1)
