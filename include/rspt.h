@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 23
+#define RSPT_ABI_VERSION 24
 
 /* error codes */
 #define RSPT_OK 0
@@ -287,10 +287,27 @@ enum {
                                     p[12] = cos_total_width, p[13] = cos_falloff_start  */
     RSPT_LIGHT_DISTANT = 4,     /* DistantLight src/lights/distant.rs:25-75: p[0..2] = w_light (normalised), L = L;
                                     the world radius comes from the scene bounds (preprocess, :76-86)      */
-    RSPT_LIGHT_INFINITE = 5     /* InfiniteAreaLight src/lights/infinite.rs:38-392: prim = index into envmaps[]
+    RSPT_LIGHT_INFINITE = 5,    /* InfiniteAreaLight src/lights/infinite.rs:38-392: prim = index into envmaps[]
                                     (texels already multiplied by L), p[0..8] = upper 3x3 of light_to_world.m,
                                     p[9..17] = upper 3x3 of world_to_light.m (row major)                    */
+    RSPT_LIGHT_PROJECTION = 6,  /* ABI 24: ProjectionLight src/lights/projection.rs:339-398: L = i (scale applied), p[0..2] = p_light,
+                                    p[3..11] = upper 3x3 of world_to_light.m (row major), p[12..15] = screen_bounds (min x, min y,
+                                    max x, max y), p[16] = hither, p[17] = cos_total_width, p[18..21] = light_projection.m[0][0],
+                                    [1][1], [2][2], [2][3] (what Transform::perspective leaves non-trivial; m[3][2] is 1),
+                                    prim = index into envmaps[] of the projection map's pyramid, or 0xffffffff: no map, and the
+                                    light projects Spectrum(1) as the reference does                                          */
+    RSPT_LIGHT_GONIOMETRIC = 7  /* ABI 24: GonioPhotometricLight src/lights/goniometric.rs:233-280: L = i, p[0..2] = p_light,
+                                    p[3..11] = upper 3x3 of world_to_light.m, prim = index into envmaps[] or 0xffffffff       */
 };
+/* The two map lights (ABI 24) are delta lights: a point light whose intensity a MipMap<Spectrum> modulates (lookup_pnt_flt(st, 0), wrap Repeat).
+ * Served: rspt_render under RSPT_INTEGRATOR_PATH with the Sobol' and Halton samplers, all three light strategies, the light table built up
+ * front; RSPT_INTEGRATOR_AO (it reads no lights); rspt_light_distribution (uniform, power, spatial).  Such a scene takes shade-stage
+ * instantiations of its own and keeps its path slots for life (no MOVE schedule).  rspt_render answers RSPT_E_UNSUPPORTED, naming "projection"
+ * or "goniometric" and what is missing, for the directlighting / whitted / volpath integrators, the four pixel samplers, a spatial light table
+ * too large to build up front (more bytes than RSPT_LIGHT_TABLE_EAGER_BYTES: rspt_light_distribution answers the same) and such a light next
+ * to analytic spheres: the caller keeps its CPU loop.  sample_le / pdf_le (bidirectional methods) are not on the device.
+ * rspt_scene_create answers RSPT_E_INVALID, naming the light, for non-finite parameters, prim neither in range nor the sentinel, and
+ * screen_bounds with min > max. */
 typedef struct {
     uint32_t kind;
     uint32_t prim;       /* DIFFUSE_AREA: BVH-ordered primitive index of the emitting triangle */
@@ -299,7 +316,7 @@ typedef struct {
     float p[24];         /* kind-specific parameters, see above                       */
 } rspt_light; /* 120 B */
 
-/* Environment map of an InfiniteAreaLight: the MipMap<Spectrum> pyramid rs_pbrt built
+/* Environment map of an InfiniteAreaLight (or, ABI 24, the map of a projection / goniometric light): the MipMap<Spectrum> pyramid rs_pbrt built
  * (src/core/mipmap.rs:56-196; power-of-two levels after its resampling, wrap mode Repeat) and the
  * scalar image its Distribution2D was built from (infinite.rs:120-137: lookup(st, fwidth).y() *
  * sin(theta) on a 2w x 2h grid).  The library rebuilds the conditional / marginal CDFs with
@@ -311,7 +328,8 @@ typedef struct {
     const float* texels;     /* rgb triples, levels concatenated; level i is
                                 max(1, width >> i) x max(1, height >> i), row major [t][s] */
     uint32_t dist_nu, dist_nv;
-    const float* dist_func;  /* [dist_nv][dist_nu]                                         */
+    const float* dist_func;  /* [dist_nv][dist_nu]; ABI 24: NULL with dist_nu = dist_nv = 0 for a map that only projection /
+                                goniometric lights name (they never sample it); an INFINITE light needs its distribution   */
 } rspt_envmap;
 
 /* ---- object instancing --------------------------------------------

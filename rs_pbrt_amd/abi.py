@@ -4,7 +4,7 @@ Every struct here must stay byte-compatible with the header; tests/test_abi.py c
 sizes against the values the library reports."""
 import ctypes as C
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 OK, E_INVALID, E_NODEVICE, E_HIP, E_UNSUPPORTED, E_NOMEM, E_PEER = 0, -1, -2, -3, -4, -5, -6
 
@@ -14,6 +14,7 @@ FRESNEL_NOOP, FRESNEL_DIELECTRIC, FRESNEL_CONDUCTOR = 0, 1, 2
 MAT_MATTE, MAT_PLASTIC, MAT_MIRROR, MAT_GLASS, MAT_METAL, MAT_SUBSTRATE, MAT_UBER, MAT_TRANSLUCENT, MAT_MIX = range(1, 10)
 LOBE_REMAP, LOBE_NODIFF = 1, 2
 LIGHT_DIFFUSE_AREA, LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT, LIGHT_INFINITE = 1, 2, 3, 4, 5
+LIGHT_PROJECTION, LIGHT_GONIOMETRIC = 6, 7      # ABI 24: p[] as include/rspt.h lays it out; prim = the map in envmaps[] or 0xffffffff
 SAMPLER_SOBOL, SAMPLER_HALTON, SAMPLER_RANDOM, SAMPLER_ZEROTWO, SAMPLER_STRATIFIED, SAMPLER_MAXMINDIST = 1, 2, 3, 4, 5, 6
 INTEGRATOR_PATH, INTEGRATOR_AO, INTEGRATOR_DIRECT, INTEGRATOR_VOLPATH, INTEGRATOR_WHITTED = 0, 1, 2, 3, 4
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2

@@ -32,11 +32,16 @@ enum : uint32_t {
     SF_SPHERE = 1u << 25,      // analytic spheres (dev_sphere.h): a hit record with MF_SPHERE builds its Hit from sphere_hit
     SF_TRIS_ONLY = 1u << 26,   // never a scene's need: set in every feature set built before spheres (SV_GENERIC, SV_DYNAMIC and SF_ALL derive from SF_ALL
                                // and so carry SF_SPHERE too); a set compiles the sphere arm only with SF_SPHERE and WITHOUT this bit (shade_sph)
+    SF_L_MAP = 1u << 27,       // ABI 24: a ProjectionLight or GonioPhotometricLight (dev_scene.h map_light_li): a delta light whose intensity a MipMap<Spectrum> modulates
+    SF_NO_MAPLIGHT = 1u << 28, // never a scene's need, as SF_TRIS_ONLY: set in every feature set built before those two lights (the sets derived from SF_ALL carry
+                               // SF_L_MAP too); a set compiles their arms only with SF_L_MAP and WITHOUT this bit (shade_ml)
     SF_ALL = 0xffffffffu
 };
 #define RSPT_SF_LOBE(T) (1u << (T))
 // does instantiation F carry the sphere arm?  Only the sphere variants (tu_decl.h SV_*_SPH) do: the triangle sets keep their code and figures
 constexpr bool shade_sph(uint32_t F) { return (F & SF_SPHERE) && !(F & SF_TRIS_ONLY); }
+// ... and the projection / goniometric arms?  Only the map-light variants (tu_decl.h SV_*_ML), and with them every caller that passes no F (0xffffffff) keeps its code
+constexpr bool shade_ml(uint32_t F) { return (F & SF_L_MAP) && !(F & SF_NO_MAPLIGHT); }
 
 // trigonometry in the shading frame, reflection.rs:1801-1886
 RDEV float cos2_t(f3 w) { return w.z * w.z; }

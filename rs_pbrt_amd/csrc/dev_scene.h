@@ -557,6 +557,8 @@ RDEV LightSample tri_sample_ref(const SceneDev& sc, uint32_t prim, const TriRec&
 }
 template <uint32_t F = 0xffffffffu>
 RDEV bool light_is_delta(const rspt_light& lt) {  // light.rs:178-188
+    if constexpr (shade_ml(F))   // LightFlags::DeltaPosition (projection.rs:189, goniometric.rs:140)
+        if (lt.kind == RSPT_LIGHT_PROJECTION || lt.kind == RSPT_LIGHT_GONIOMETRIC) return true;
     return ((F & SF_L_POINT) && lt.kind == RSPT_LIGHT_POINT) || ((F & SF_L_SPOT) && lt.kind == RSPT_LIGHT_SPOT) || ((F & SF_L_DISTANT) && lt.kind == RSPT_LIGHT_DISTANT);
 }
 // ---- MipMap<Spectrum> lookups, wrap mode Repeat (mipmap.rs:206-252, 323-336) ----
@@ -650,6 +652,35 @@ RDEV float spot_falloff(const rspt_light& lt, f3 w) {  // spot.rs:67-80
     float delta = (c - c_total) / (c_start - c_total);
     return (delta * delta) * (delta * delta);
 }
+// ---- ProjectionLight / GonioPhotometricLight (ABI 24; src/lights/projection.rs, goniometric.rs): the map-light instantiations only (dev_bsdf.h shade_ml) ----
+// rspt_light.prim = the light's pyramid in envmaps[], or RSPT_MISS: no map, and the reference takes Spectrum(1)
+// ProjectionLight::projection (projection.rs:339-360).  p[18..21] = light_projection.m[0][0], [1][1], [2][2], [2][3]; every other entry is the +0 (and
+// m[3][2] the 1) that Transform::perspective leaves (transform.rs:461-489), and transform_point (:490-517) is evaluated with those terms in place:
+// 0 * inf is NaN and -0 + 0 is +0, as in the reference
+RDEVN rgb projection_light_map(const SceneDev& sc, const rspt_light& lt, f3 w) {
+    const f3 wl = mat3_mul(lt.p + 3, w);   // world_to_light.transform_vector
+    if (wl.z < lt.p[16]) return mkrgb(0.0f);   // behind the hither plane
+    const float x = wl.x, y = wl.y, z = wl.z;
+    float xp = lt.p[18] * x + 0.0f * y + 0.0f * z + 0.0f;
+    float yp = 0.0f * x + lt.p[19] * y + 0.0f * z + 0.0f;
+    const float wp = 0.0f * x + 0.0f * y + 1.0f * z + 0.0f;
+    if (wp != 1.0f) { const float inv = 1.0f / wp; xp = inv * xp; yp = inv * yp; }   // (p.z is not read)
+    const float x0 = lt.p[12], y0 = lt.p[13], x1 = lt.p[14], y1 = lt.p[15];
+    if (!(xp >= x0 && xp <= x1 && yp >= y0 && yp <= y1)) return mkrgb(0.0f);   // pnt2_inside_bnd2f (geometry.rs:990-992)
+    if (lt.prim == RSPT_MISS) return mkrgb(1.0f);
+    f2 st{xp - x0, yp - y0};   // Bounds2f::offset (geometry.rs:1891-1900)
+    if (x1 > x0) st.x /= x1 - x0;
+    if (y1 > y0) st.y /= y1 - y0;
+    return env_lookup(sc.envmaps[lt.prim], st, 0.0f);
+}
+// GonioPhotometricLight::scale (goniometric.rs:233-247)
+RDEVN rgb goniometric_light_map(const SceneDev& sc, const rspt_light& lt, f3 w) {
+    const f3 v = normalize(mat3_mul(lt.p + 3, w));
+    const f3 wp{v.x, v.z, v.y};   // std::mem::swap(&mut wp.y, &mut wp.z)
+    const float theta = spherical_theta(wp), phi = spherical_phi(wp);
+    if (lt.prim == RSPT_MISS) return mkrgb(1.0f);
+    return env_lookup(sc.envmaps[lt.prim], f2{phi * RSPT_INV_2_PI, theta * RSPT_INV_PI}, 0.0f);
+}
 // Light::sample_li: DiffuseAreaLight (diffuse.rs:64-84), PointLight (point.rs:52-68), SpotLight
 // (spot.rs:81-106), DistantLight (distant.rs:41-58).  Delta lights return pdf = 1 and a light point
 // with zero normal and zero error bounds (InteractionCommon::default()).
@@ -679,6 +710,14 @@ RDEV rgb light_sample_li(const SceneDev& sc, const rspt_light& lt, f3 ref_p, f2 
         return env_lookup(m, uv, 0.0f);
     }
     *pdf = 1.0f;
+    if constexpr (shade_ml(F))
+        if (lt.kind == RSPT_LIGHT_PROJECTION || lt.kind == RSPT_LIGHT_GONIOMETRIC) {  // projection.rs:362-378, goniometric.rs:249-265: i * map(-wi) / d^2
+            const f3 pl{lt.p[0], lt.p[1], lt.p[2]};
+            *wi = normalize(pl - ref_p);
+            ls->p = pl;
+            const rgb m = lt.kind == RSPT_LIGHT_PROJECTION ? projection_light_map(sc, lt, -*wi) : goniometric_light_map(sc, lt, -*wi);
+            return ldrgb(lt.L) * m / dist2(pl, ref_p);
+        }
     if ((F & SF_L_DISTANT) && lt.kind == RSPT_LIGHT_DISTANT) {
         f3 w{lt.p[0], lt.p[1], lt.p[2]};
         *wi = w;
@@ -692,8 +731,15 @@ RDEV rgb light_sample_li(const SceneDev& sc, const rspt_light& lt, f3 ref_p, f2 
     if (!(F & SF_L_SPOT) || lt.kind == RSPT_LIGHT_POINT) return ldrgb(lt.L) / d2;
     return ldrgb(lt.L) * spot_falloff(lt, -*wi) / d2;
 }
-// Light::power (diffuse.rs:85-93, point.rs:69-71, spot.rs:107-113, distant.rs:59-62)
+// Light::power (diffuse.rs:85-93, point.rs:69-71, spot.rs:107-113, distant.rs:59-62); F as in light_sample_li
+template <uint32_t F = 0xffffffffu>
 RDEV rgb light_power(const SceneDev& sc, const rspt_light& lt) {
+    if constexpr (shade_ml(F))
+        if (lt.kind == RSPT_LIGHT_PROJECTION || lt.kind == RSPT_LIGHT_GONIOMETRIC) {  // projection.rs:379-398, goniometric.rs:266-280: ((map * i) * k) * PI [* (1 - cos_total_width)]
+            const rgb m = lt.prim == RSPT_MISS ? mkrgb(1.0f) : env_lookup(sc.envmaps[lt.prim], f2{0.5f, 0.5f}, 0.5f);
+            if (lt.kind == RSPT_LIGHT_GONIOMETRIC) return m * ldrgb(lt.L) * 4.0f * RSPT_PI;
+            return m * ldrgb(lt.L) * 2.0f * RSPT_PI * (1.0f - lt.p[17]);
+        }
     if (lt.kind == RSPT_LIGHT_POINT) return ldrgb(lt.L) * (4.0f * RSPT_PI);
     if (lt.kind == RSPT_LIGHT_SPOT) return ldrgb(lt.L) * 2.0f * RSPT_PI * (1.0f - 0.5f * (lt.p[13] + lt.p[12]));
     if (lt.kind == RSPT_LIGHT_DISTANT) { float r = world_radius(sc); return ldrgb(lt.L) * RSPT_PI * r * r; }

@@ -1561,7 +1561,8 @@ RDEV float radical_inverse(int base_index, uint64_t a) {  // lowdiscrepancy.rs:1
     }
     return fminf((float)reversed * inv_base_n, RSPT_ONE_MINUS_EPS);
 }
-// SpatialLightDistribution::compute_distribution, per (voxel, light) (lightdistrib.rs:169-260)
+// SpatialLightDistribution::compute_distribution, per (voxel, light) (lightdistrib.rs:169-260); F as in light_sample_li
+template <uint32_t F = 0xffffffffu>
 RDEV float ld_voxel_light_contrib(const SceneDev& sc, int32_t nvx, int32_t nvy, int32_t nvz, uint64_t v, uint32_t j) {
     int32_t ix = (int32_t)(v % nvx), iy = (int32_t)((v / nvx) % nvy), iz = (int32_t)(v / ((uint64_t)nvx * nvy));
     f3 wmin{sc.wb_min[0], sc.wb_min[1], sc.wb_min[2]}, wmax{sc.wb_max[0], sc.wb_max[1], sc.wb_max[2]};
@@ -1578,7 +1579,7 @@ RDEV float ld_voxel_light_contrib(const SceneDev& sc, int32_t nvx, int32_t nvy, 
         float pdf = 0.0f;
         f3 wi{0.0f, 0.0f, 0.0f};
         LightSample ls;
-        rgb li = light_sample_li(sc, lt, po, u, &wi, &pdf, &ls);
+        rgb li = light_sample_li<F>(sc, lt, po, u, &wi, &pdf, &ls);
         if (pdf > 0.0f) contrib += lum(li) / pdf;
     }
     return contrib;
@@ -1588,6 +1589,20 @@ RSPT_PLAIN_KERNEL void k_ld_contrib(SceneDev sc, int32_t nvx, int32_t nvy, int32
     uint64_t total = (uint64_t)nvx * nvy * nvz * sc.n_lights;
     if (gid >= total) return;
     func[gid] = ld_voxel_light_contrib(sc, nvx, nvy, nvz, gid / sc.n_lights, (uint32_t)(gid % sc.n_lights));
+}
+// the same two over a scene with projection / goniometric lights (ABI 24): the only light-table kernels that carry those arms (dev_bsdf.h shade_ml)
+constexpr uint32_t LD_MAPLIGHT = 0xffffffffu & ~SF_NO_MAPLIGHT;
+RSPT_PLAIN_KERNEL void k_ld_contrib_ml(SceneDev sc, int32_t nvx, int32_t nvy, int32_t nvz, float* __restrict__ func) {
+    uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t total = (uint64_t)nvx * nvy * nvz * sc.n_lights;
+    if (gid >= total) return;
+    func[gid] = ld_voxel_light_contrib<LD_MAPLIGHT>(sc, nvx, nvy, nvz, gid / sc.n_lights, (uint32_t)(gid % sc.n_lights));
+}
+RSPT_PLAIN_KERNEL void k_ld_fixed_ml(SceneDev sc, int power, float* __restrict__ func) {
+    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= sc.n_lights) return;
+    if (!power) { func[j] = 1.0f; return; }
+    func[j] = lum(light_power<LD_MAPLIGHT>(sc, sc.lights[j]));
 }
 // one Distribution1D per voxel (sampling.rs:24-49) after the min-contribution clamp (:262-268);
 // mode 0: spatial (func holds raw contributions), 1: use func as is (uniform / power)

@@ -242,15 +242,21 @@ const ShadeVariant g_shade_variants[] = {
     // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
     {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
     {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
+    // scenes with a projection or goniometric light (ABI 24, SF_L_MAP; Sobol' and Halton): the generic and the all-features set with the two arms of
+    // light_sample_li / light_is_delta (dev_bsdf.h shade_ml).  Only such scenes take them and such scenes take nothing else.  No MOVE form: the
+    // schedule was left off for them (unmeasured there), they keep slots for life.
+    {SV_GENERIC_ML, "generic-maplight", k_shade<SV_GENERIC_ML>, k_shade<SV_GENERIC_ML>, k_shade<SV_GENERIC_ML>, 0, nullptr},
+    {SV_ALL_ML, "all-maplight", k_shade<SV_ALL_ML>, k_shade<SV_ALL_ML>, k_shade<SV_ALL_ML>, 0, nullptr},
 };
 // RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
 // move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)
 ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
     const char* force = getenv("RSPT_SHADE_VARIANT");
     if (move_out) *move_out = nullptr;
-    const bool sph = (need & SF_SPHERE) != 0;
+    const bool sph = (need & SF_SPHERE) != 0, ml = (need & SF_L_MAP) != 0;
     for (const ShadeVariant& v : g_shade_variants) {
         if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
+        if (shade_ml(v.features) != ml) continue;     // (... and SF_L_MAP: SF_NO_MAPLIGHT)
         if ((need & ~v.features) != 0) continue;
         if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;
         if (name_out) *name_out = v.name;
@@ -258,6 +264,6 @@ ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* 
         if (move_out && waves == (size_t)v.dflt) *move_out = v.move;
         return waves == 3 ? v.w3 : (waves == 4 ? v.w4 : v.natural);
     }
-    if (sph) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)
+    if (sph || ml) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)
     return k_shade<SF_ALL>;
 }

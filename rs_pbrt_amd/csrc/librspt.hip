@@ -263,6 +263,8 @@ struct rspt_scene_s {
     std::vector<uint64_t> image_base; // per image: its first float in the texel pool
     bool has_instances = false;       // object instances: two-level traversal (kernels.h traverse<ANY, true>)
     bool has_animated = false;        // ... some of them moving (dev_scene.h inst_at): the reference-order kernel serves the scene, `path` under Sobol' / Halton only
+    const char* maplight_kinds = "";   // "projection", "goniometric" or "projection and goniometric": which of the two the scene holds, for the refusals
+    bool has_maplights = false;       // ABI 24: a projection or goniometric light (dev_scene.h light_sample_li's two arms); rspt_render serves them under path (Sobol', Halton) and ao
     bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); rspt_render serves them under path / ao (Sobol', Halton)
     bool has_sphere_light = false;    // an emissive sphere: refused by rspt_render and the light-distribution hook (sphere area lights are not on the device)
     std::map<int, LightDist> light_dists;  // by effective strategy
@@ -515,6 +517,8 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             lazy = n_vox * row_bytes > env_size("RSPT_LIGHT_TABLE_EAGER_BYTES", (size_t)1 << 30);
             n_rows = n_vox;
             if (lazy) n_rows = std::max<uint64_t>(1, std::min<uint64_t>(n_vox, env_size("RSPT_LIGHT_TABLE_POOL_BYTES", (size_t)16 << 30) / row_bytes));
+            // (the on-demand kernels carry no projection / goniometric arm: such a scene takes the table built up front or nothing)
+            if (lazy && s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)", s->maplight_kinds);
             if (n_rows > 0x7fffffffull || n_vox > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "spatial light distribution: %llu voxels", (unsigned long long)n_vox);
         }
         int rc;
@@ -529,10 +533,10 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             HIP_TRY(hipMemcpyAsync(d.lazy, &lz, sizeof lz, hipMemcpyHostToDevice, g.stream));
         } else if (eff == RSPT_LIGHTS_SPATIAL) {
             uint64_t total = n_vox * nl;
-            hipLaunchKernelGGL(k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
+            hipLaunchKernelGGL(s->has_maplights ? k_ld_contrib_ml : k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
             hipLaunchKernelGGL(k_ld_build, dim3((uint32_t)((n_vox + 255) / 256)), dim3(256), 0, g.stream, (uint32_t)n_vox, nl, 0, d.func, d.cdf, d.func_int);
         } else {
-            hipLaunchKernelGGL(k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
+            hipLaunchKernelGGL(s->has_maplights ? k_ld_fixed_ml : k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
             hipLaunchKernelGGL(k_ld_build, dim3(1), dim3(64), 0, g.stream, 1u, nl, 1, d.func, d.cdf, d.func_int);
         }
         HIP_TRY(hipGetLastError());
@@ -837,13 +841,25 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             if (p.mesh < d->n_meshes && p.area_light >= 0 && (d->meshes[p.mesh].alpha_tex || d->meshes[p.mesh].shadow_alpha_tex))
                 return fail(RSPT_E_UNSUPPORTED, "prim %llu: an emissive mesh with an alpha mask", (unsigned long long)i);
         }
+    bool has_maplights = false, has_projection = false, has_goniometric = false;
     for (uint32_t i = 0; i < d->n_lights; i++) {
-        if (d->lights[i].kind < RSPT_LIGHT_DIFFUSE_AREA || d->lights[i].kind > RSPT_LIGHT_INFINITE) return fail(RSPT_E_UNSUPPORTED, "light %u: unsupported kind %u", i, d->lights[i].kind);
+        if (d->lights[i].kind < RSPT_LIGHT_DIFFUSE_AREA || d->lights[i].kind > RSPT_LIGHT_GONIOMETRIC) return fail(RSPT_E_UNSUPPORTED, "light %u: unsupported kind %u", i, d->lights[i].kind);
         if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->lights[i].prim >= n_top_prims || d->prims[d->lights[i].prim].mesh == RSPT_MESH_INSTANCE))   // (a sphere primitive may be named, ABI 23)
             return fail(RSPT_E_INVALID, "light %u: prim out of range", i);
         if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && d->prims[d->lights[i].prim].mesh == RSPT_MESH_SPHERE && d->prims[d->lights[i].prim].area_light != (int32_t)i)
             return fail(RSPT_E_INVALID, "light %u: its sphere primitive names another light", i);
         if (d->lights[i].kind == RSPT_LIGHT_INFINITE && d->lights[i].prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u: envmap index out of range", i);
+        if (d->lights[i].kind == RSPT_LIGHT_PROJECTION || d->lights[i].kind == RSPT_LIGHT_GONIOMETRIC) {   // ABI 24
+            const rspt_light& l = d->lights[i];
+            const char* kn = l.kind == RSPT_LIGHT_PROJECTION ? "projection" : "goniometric";
+            const int n_par = l.kind == RSPT_LIGHT_PROJECTION ? 22 : 12;
+            for (int k = 0; k < 3; k++) if (!std::isfinite(l.L[k])) return fail(RSPT_E_INVALID, "light %u (%s): non-finite intensity", i, kn);
+            for (int k = 0; k < n_par; k++) if (!std::isfinite(l.p[k])) return fail(RSPT_E_INVALID, "light %u (%s): non-finite parameter p[%d]", i, kn, k);
+            if (l.prim != 0xffffffffu && l.prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u (%s): map index out of range", i, kn);
+            if (l.kind == RSPT_LIGHT_PROJECTION && (l.p[12] > l.p[14] || l.p[13] > l.p[15])) return fail(RSPT_E_INVALID, "light %u (projection): screen_bounds min above max", i);
+            has_maplights = true;
+            (l.kind == RSPT_LIGHT_PROJECTION ? has_projection : has_goniometric) = true;
+        }
     }
     // textures: constant / imagemap / scale; each material may bind at most RSPT_TEX_SLOTS distinct ones
     if ((d->n_textures && !d->textures) || (d->n_images && !d->images)) return fail(RSPT_E_INVALID, "null texture / image array");
@@ -937,7 +953,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
         shade_features |= SF_DYNAMIC | SF_TEX | 0x3feu | SF_CONDUCTOR | SF_SC;
     for (uint32_t i = 0; i < d->n_lights; i++) {
         const uint32_t k = d->lights[i].kind;
-        shade_features |= k == RSPT_LIGHT_DIFFUSE_AREA ? SF_L_AREA : (k == RSPT_LIGHT_POINT ? SF_L_POINT : (k == RSPT_LIGHT_SPOT ? SF_L_SPOT : (k == RSPT_LIGHT_DISTANT ? SF_L_DISTANT : SF_L_INFINITE)));
+        shade_features |= k == RSPT_LIGHT_DIFFUSE_AREA ? SF_L_AREA : (k == RSPT_LIGHT_POINT ? SF_L_POINT : (k == RSPT_LIGHT_SPOT ? SF_L_SPOT : (k == RSPT_LIGHT_DISTANT ? SF_L_DISTANT : (k == RSPT_LIGHT_INFINITE ? SF_L_INFINITE : SF_L_MAP))));
     }
     for (uint32_t i = 0; i < d->n_meshes; i++)
         if (d->meshes[i].has_n || d->meshes[i].has_s || d->meshes[i].has_uv) shade_features |= SF_VERTEX;
@@ -951,7 +967,14 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
         uint32_t nl = 1;
         for (uint32_t m = std::max(e.width, e.height); m > 1; m >>= 1) nl++;
         if (e.n_levels != nl || nl > 16) return fail(RSPT_E_INVALID, "envmap %u: n_levels %u, expected %u", i, e.n_levels, nl);
-        if (!e.texels || !e.dist_func || e.dist_nu == 0 || e.dist_nv == 0) return fail(RSPT_E_INVALID, "envmap %u: null data", i);
+        // ABI 24: a map that only projection / goniometric lights name carries no distribution (they never sample it); an infinite light needs its own
+        bool sampled = false, named = false;
+        for (uint32_t l = 0; l < d->n_lights; l++) {
+            if (d->lights[l].kind == RSPT_LIGHT_INFINITE && d->lights[l].prim == i) sampled = true;
+            if ((d->lights[l].kind == RSPT_LIGHT_PROJECTION || d->lights[l].kind == RSPT_LIGHT_GONIOMETRIC) && d->lights[l].prim == i) named = true;
+        }
+        const bool no_dist = !e.dist_func && e.dist_nu == 0 && e.dist_nv == 0;
+        if (!e.texels || !((named && !sampled && no_dist) || (e.dist_func && e.dist_nu != 0 && e.dist_nv != 0))) return fail(RSPT_E_INVALID, "envmap %u: null data", i);
     }
     // BVH: child / leaf ranges in bounds, depth <= 64 (the reference's fixed traversal stack, bvh.rs:420); with instances the
     // object's traversal continues on the stack of the top-level one (kernels.h traverse), so the two depths add up
@@ -999,6 +1022,8 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     s->has_null_material = has_null || (instanced && d->instancing_mode == RSPT_INSTANCING_REFERENCE);  // instanced hits pass through like null surfaces (Q11)
     s->has_instances = instanced;
     s->has_alpha = any_alpha;
+    s->has_maplights = has_maplights;
+    s->maplight_kinds = has_projection ? (has_goniometric ? "projection and goniometric" : "projection") : (has_goniometric ? "goniometric" : "");
     s->n_materials = d->n_materials;
     s->shade_features = shade_features;
     s->shade_classes = shade_classes;
@@ -1144,6 +1169,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
                 n_tex += (size_t)w * h;
             }
             if ((rc = upload(s, e.texels, n_tex * 3, &m.texels))) return bail(rc);
+            if (!e.dist_func) continue;   // (ABI 24) the map of a projection / goniometric light: the pyramid alone, the distribution pointers stay null
             // Distribution2D::new (sampling.rs:156-170) = Distribution1D::new (:24-49) per row and for the marginal
             const uint32_t nu = e.dist_nu, nv = e.dist_nv;
             std::vector<float> cdf((size_t)nv * (nu + 1)), fint(nv), mcdf(nv + 1);
@@ -1693,6 +1719,7 @@ int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3],
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
     // (a scene whose spheres are no lights needs no sphere code here: the spatial voxels take the world bound from the BVH root, which holds the spheres)
     if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
+    // (a scene with projection / goniometric lights: get_light_dist launches the kernels that carry their arms, and refuses the on-demand table)
     const uint32_t nl = s->dev.n_lights;
     if (nl == 0) return fail(RSPT_E_INVALID, "the scene has no lights");
     HIP_TRY(hipSetDevice(g.device));

@@ -81,6 +81,20 @@ int RenderRun::validate() {
         if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "sphere scene with more four-box records than a reference holds");
         if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with spheres: the sphere traversal keeps no node counters");
     }
+    // ABI 24: projection and goniometric lights are served where their two arms of light_sample_li / light_is_delta are compiled: the path integrator's wavefront
+    // form under Sobol' / Halton (the map-light shade instantiations, launch_trace.h) and ao, which reads no lights.  The per-lane and per-tile walks of the other
+    // integrators and of the pixel samplers keep their code, so everything else is refused and the caller keeps its CPU loop.
+    if (s->has_maplights) {
+        static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
+        const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
+        if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+            return fail(RSPT_E_UNSUPPORTED, "scene with a %s light under the %s integrator: these lights are served by path (and ao, which reads none) only", s->maplight_kinds, iname);
+        if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+            return fail(RSPT_E_UNSUPPORTED, "scene with a %s light under the %s sampler: these lights are served with the sobol and halton samplers only", s->maplight_kinds,
+                        d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                        d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+        if (s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light next to analytic spheres: that pair has no shade instantiation yet", s->maplight_kinds);
+    }
     // WhittedIntegrator::li runs on directlighting's machinery (direct.h / dl_serial.h, their WH forms) as UniformSampleAll with one estimate per light and
     // no sample arrays; max_depth 0 recurses no more than 1 does (whitted.rs:103: depth + 1 < max_depth)
     whitted = d->integrator == RSPT_INTEGRATOR_WHITTED;
@@ -358,7 +372,8 @@ int RenderRun::size_batches() {
     // round 6: the path integrator's MOVING path state (kernels.h PathBuf::move) — wherever the scene's shade instantiation has a MOVE form; not with moving instances
     // (their ray times are kept by original slot) and not under the pixel samplers / the other integrators, which keep slots for life.  RSPT_MOVE=0: slots, as before.
     shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k);
-    if (!shade_k) return fail(RSPT_E_UNSUPPORTED, "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
+    if (!shade_k) return fail(RSPT_E_UNSUPPORTED, s->has_maplights ? "RSPT_SHADE_VARIANT names no instantiation with the projection / goniometric arms (generic-maplight, all-maplight)"
+                                                                  : "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
     move = !volpath && !direct && !ao && !pixel_sampler && !s->has_animated && shade_move_k != nullptr && env_size("RSPT_MOVE", 1) != 0;
     // the first iteration that runs the MOVE kernel.  Iteration 0 reads a dense pixel-major queue whatever the schedule and its stores are dense too (every slot is
     // written): the slot-for-life kernel serves it (the MOVE form is 4 % slower there: 120 B of scratch against 36 at the same 168 VGPRs, profiles/r06_move_ab.txt),

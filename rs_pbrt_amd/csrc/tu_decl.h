@@ -22,6 +22,9 @@ constexpr uint32_t SV_DIFFUSE_H = (SV_DIFFUSE & ~SF_SOBOL) | SF_HALTON, SV_PLAST
 constexpr uint32_t SV_DYNAMIC = SF_ALL & ~SF_ANIM;                                                  // + per-hit lobe lists; SF_ALL itself: + moving instances
 // scenes with analytic spheres (dev_bsdf.h shade_sph): the generic and the dynamic set with the sphere arm; the sets above keep SF_TRIS_ONLY and so their code
 constexpr uint32_t SV_GENERIC_SPH = SV_GENERIC & ~SF_TRIS_ONLY, SV_DYNAMIC_SPH = SV_DYNAMIC & ~SF_TRIS_ONLY;
+// scenes with a projection or goniometric light (ABI 24; dev_bsdf.h shade_ml): the generic set and the all-features set with those two arms; every set above
+// keeps SF_NO_MAPLIGHT (or never had SF_L_MAP) and so its code
+constexpr uint32_t SV_GENERIC_ML = SV_GENERIC & ~SF_NO_MAPLIGHT, SV_ALL_ML = SF_ALL & ~SF_NO_MAPLIGHT;
 
 #define RSPT_TU_TS(I, A, M) \
     RSPT_TU_X template __global__ void k_tile_serial<I, A, M>(SceneDev, TexTables, LightDistDev, RenderDev, PathBuf, PixDesc, const TileRec*, uint32_t, uint32_t, int32_t, int32_t, float4*, float2*, uint32_t, uint32_t*);
@@ -149,6 +152,9 @@ RSPT_TU_SHADE(SV_DYNAMIC) RSPT_TU_SHADE(SF_ALL)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_S)
 RSPT_TU_SHADE(SV_GENERIC_SPH) RSPT_TU_SHADE(SV_DYNAMIC_SPH)   /* scenes with spheres; no MOVE form: they keep slots for life */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_L)
+RSPT_TU_SHADE(SV_GENERIC_ML) RSPT_TU_SHADE(SV_ALL_ML)   /* scenes with projection / goniometric lights; no MOVE form */
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_H)
 RSPT_TU_SHADE(SV_DIFFUSE_H) RSPT_TU_SHADE_W(SV_DIFFUSE_H, 3) RSPT_TU_SHADE(SV_PLASTIC_H) RSPT_TU_SHADE_W(SV_PLASTIC_H, 3) RSPT_TU_SHADE(SV_TEXTURED_H) RSPT_TU_SHADE_W(SV_TEXTURED_H, 3)

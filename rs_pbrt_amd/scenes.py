@@ -149,6 +149,17 @@ def _v3_normalize(v):
     return (F32(x * inv), F32(y * inv), F32(z * inv))
 
 
+def _transform_point(m, p):
+    """Transform::transform_point (transform.rs:490-517) in f32: the four row sums left to right, the division by wp unless it is exactly 1"""
+    x, y, z = (F32(c) for c in p)
+    row = lambda i: F32(F32(F32(F32(m[i, 0] * x) + F32(m[i, 1] * y)) + F32(m[i, 2] * z)) + m[i, 3])      # noqa: E731
+    xp, yp, zp, wp = row(0), row(1), row(2), row(3)
+    if wp == F32(1):
+        return (xp, yp, zp)
+    inv = F32(F32(1) / wp)
+    return (F32(inv * xp), F32(inv * yp), F32(inv * zp))
+
+
 def _v3_cross(a, b):
     """vec3_cross_vec3: the products and differences in f64, rounded once (geometry.rs:680-692)"""
     ax, ay, az = (float(F32(c)) for c in a); bx, by, bz = (float(F32(c)) for c in b)
@@ -348,10 +359,8 @@ def _env_triangle(level_img, s_, t_):  # MipMap::triangle (mipmap.rs:323-336), w
     return (((tmp4 + tmp3).astype(F32) + tmp2).astype(F32) + tmp1).astype(F32)
 
 
-def build_envmap(texels):
-    """texels (h, w, 3) f32, power-of-two sides (rs_pbrt resamples other sizes first, mipmap.rs:64-148).
-    Returns the MIP pyramid (mipmap.rs:154-185) and the scalar image of the sampling distribution
-    (infinite.rs:120-137)."""
+def _env_pyramid(texels):
+    """the MipMap<Spectrum> pyramid (mipmap.rs:154-185, wrap Repeat) of texels (h, w, 3) f32 with power-of-two sides: the list of its levels"""
     img = np.ascontiguousarray(texels, F32)
     h, w, _ = img.shape
     assert w & (w - 1) == 0 and h & (h - 1) == 0, "environment map sides must be powers of two"
@@ -365,6 +374,24 @@ def build_envmap(texels):
         tex = lambda a, b: p[np.mod(b, ph), np.mod(a, pw)]  # noqa: E731
         acc = (((tex(2 * si, 2 * ti) + tex(2 * si + 1, 2 * ti)).astype(F32) + tex(2 * si, 2 * ti + 1)).astype(F32) + tex(2 * si + 1, 2 * ti + 1)).astype(F32)
         levels.append((acc * F32(0.25)).astype(F32))
+    return levels
+
+
+def build_light_map(texels):
+    """The map of a projection / goniometric light (ABI 24): the pyramid alone, no sampling distribution (those lights never sample their map)."""
+    levels = _env_pyramid(texels)
+    h, w, _ = levels[0].shape
+    return dict(width=w, height=h, n_levels=len(levels), texels=np.ascontiguousarray(np.concatenate([l.reshape(-1) for l in levels]), F32),
+                dist_nu=0, dist_nv=0, dist_func=None)
+
+
+def build_envmap(texels):
+    """texels (h, w, 3) f32, power-of-two sides (rs_pbrt resamples other sizes first, mipmap.rs:64-148).
+    Returns the MIP pyramid (mipmap.rs:154-185) and the scalar image of the sampling distribution
+    (infinite.rs:120-137)."""
+    levels = _env_pyramid(texels)
+    h, w, _ = levels[0].shape
+    n_levels = len(levels)
     nu, nv = 2 * w, 2 * h
     fwidth = F32(0.5) / F32(min(nu, nv))
     vv, uu = np.meshgrid(np.arange(nv), np.arange(nu), indexing="ij")
@@ -767,6 +794,50 @@ class SceneBuilder:
         lt["p"][:9] = l2w.reshape(-1); lt["p"][9:18] = np.linalg.inv(l2w.astype(np.float64)).astype(F32).reshape(-1)
         self.delta_lights.append(lt)
 
+    def _light_map(self, image):
+        if image is None:
+            return 0xFFFFFFFF      # no map: the light projects Spectrum(1) (projection.rs:357-359, goniometric.rs:244-246)
+        self.envmaps.append(build_light_map(np.asarray(image, F32)))
+        return len(self.envmaps) - 1
+
+    def add_projection_light(self, p_from, p_to, I, fov=45.0, image=None, up=(0.0, 1.0, 0.0)):
+        """LightSource "projection" (api.rs:866-885, ProjectionLight::new_hdr projection.rs:226-317) under a CTM of `LookAt from to up`: light_to_world is that
+        LookAt's inverse, so the light sits at `from` and projects along `to - from`.  I = I * scale.  image: (h, w, 3) f32 with power-of-two sides (the caller
+        hands over what MipMap::new would keep), or None: no map — the record keeps the geometry of a square map and the device projects Spectrum(1), as
+        ProjectionLight::projection does without one (the reference's constructor itself zeroes a map-less light).  Every step in f32."""
+        w2l = Transform.look_at(p_from, p_to, up)      # world_to_light = Transform::inverse(light_to_world): m = the LookAt matrix, m_inv = light_to_world.m
+        lt = np.zeros((), abi.LIGHT_DT)
+        lt["kind"] = abi.LIGHT_PROJECTION; lt["L"] = np.array(I, F32)
+        lt["p"][:3] = np.array(_transform_point(w2l.m_inv, (0.0, 0.0, 0.0)), F32)      # p_light = light_to_world.transform_point(origin)
+        lt["p"][3:12] = w2l.m[:3, :3].reshape(-1)
+        rx, ry = (1, 1) if image is None else (np.asarray(image).shape[1], np.asarray(image).shape[0])
+        aspect = F32(F32(rx) / F32(ry))
+        if aspect > F32(1):      # projection.rs:266-289
+            sb = (-aspect, F32(-1), aspect, F32(1))
+        else:
+            sb = (F32(-1), F32(F32(-1) / aspect), F32(1), F32(F32(1) / aspect))
+        lt["p"][12:16] = np.array(sb, F32)
+        hither, yon = F32(1e-3), F32(1e30)
+        proj = Transform.perspective(fov, hither, yon)
+        lt["p"][16] = hither
+        w_corner = _v3_normalize(_transform_point(proj.m_inv, (sb[2], sb[3], 0.0)))      # screen_to_light.transform_point(p_corner), projection.rs:293-301
+        lt["p"][17] = w_corner[2]
+        lt["p"][18:22] = np.array([proj.m[0, 0], proj.m[1, 1], proj.m[2, 2], proj.m[2, 3]], F32)
+        lt["prim"] = self._light_map(image)
+        self.delta_lights.append(lt)
+
+    def add_goniometric_light(self, light_to_world, I, image=None):
+        """LightSource "goniometric" (api.rs:846-865, GonioPhotometricLight::new_hdr goniometric.rs:167-232): light_to_world a Transform or a 4x4 matrix (its
+        inverse by Matrix4x4::inverse, as Transform::new), I = I * scale, image as for add_projection_light (a lat-long map: s = phi / 2 pi, t = theta / pi
+        around the light's y axis)."""
+        l2w = light_to_world if isinstance(light_to_world, Transform) else Transform(np.asarray(light_to_world, F32).reshape(4, 4))
+        lt = np.zeros((), abi.LIGHT_DT)
+        lt["kind"] = abi.LIGHT_GONIOMETRIC; lt["L"] = np.array(I, F32)
+        lt["p"][:3] = np.array(_transform_point(l2w.m, (0.0, 0.0, 0.0)), F32)
+        lt["p"][3:12] = l2w.m_inv[:3, :3].reshape(-1)
+        lt["prim"] = self._light_map(image)
+        self.delta_lights.append(lt)
+
     def finish(self, bvh_builder, max_prims_in_node=4, instancing="reference"):
         """bvh_builder(P (nv,3) f32, tri (nt,3) u32, max_prims) -> (nodes NODE_DT[], ordered u32[]).
         With object instances the top-level aggregate is built over (top-level triangles in declaration order, then the
@@ -998,7 +1069,8 @@ class Scene:
         p = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self._env_structs = (abi.EnvMap * max(len(self.envmaps), 1))()
         for i, e in enumerate(self.envmaps):
-            self._env_structs[i] = abi.EnvMap(e["width"], e["height"], e["n_levels"], 0, e["texels"].ctypes.data, e["dist_nu"], e["dist_nv"], e["dist_func"].ctypes.data)
+            self._env_structs[i] = abi.EnvMap(e["width"], e["height"], e["n_levels"], 0, e["texels"].ctypes.data, e["dist_nu"], e["dist_nv"],
+                                              e["dist_func"].ctypes.data if e["dist_func"] is not None else None)      # (None: the map of a projection / goniometric light, ABI 24)
         self.desc = abi.SceneDesc(p(nodes), len(nodes), p(prims), len(prims), p(meshes), len(meshes),
                                   p(P), p(N), p(S), p(UV), len(P),
                                   p(materials), len(materials), p(lights), len(lights),

@@ -325,9 +325,40 @@ fn light_record(f: &mut Flat, l: &Light, index: usize) -> Result<RsptLight, Stri
             o.p[12] = s.cos_total_width; o.p[13] = s.cos_falloff_start;
         }
         Light::Distant(d) => { o.kind = 4; o.l = d.l.c; o.p[..3].copy_from_slice(&[d.w_light.x, d.w_light.y, d.w_light.z]); } // distant.rs:25-75
-        _ => return Err("light without a GPU form (projection / goniometric)".into()),
+        Light::Projection(pl) => {                                                 // ABI 24; projection.rs:47-63, :339-398
+            o.kind = 6; o.l = pl.i.c; o.p[..3].copy_from_slice(&[pl.p_light.x, pl.p_light.y, pl.p_light.z]);
+            let w = &pl.world_to_light.m.m;
+            for r in 0..3 { for c in 0..3 { o.p[3 + 3 * r + c] = w[r][c]; } }
+            let sb = &pl.screen_bounds;
+            o.p[12..16].copy_from_slice(&[sb.p_min.x, sb.p_min.y, sb.p_max.x, sb.p_max.y]);
+            o.p[16] = pl.hither; o.p[17] = pl.cos_total_width;
+            let m = &pl.light_projection.m.m;                                      // Transform::perspective (transform.rs:461-489): the rest is +0, m[3][2] = 1
+            o.p[18..22].copy_from_slice(&[m[0][0], m[1][1], m[2][2], m[2][3]]);
+            o.prim = light_map(f, &pl.projection_map);
+        }
+        Light::GonioPhotometric(g) => {                                            // ABI 24; goniometric.rs:38-48, :233-280
+            o.kind = 7; o.l = g.i.c; o.p[..3].copy_from_slice(&[g.p_light.x, g.p_light.y, g.p_light.z]);
+            let w = &g.world_to_light.m.m;
+            for r in 0..3 { for c in 0..3 { o.p[3 + 3 * r + c] = w[r][c]; } }
+            o.prim = light_map(f, &g.mipmap);
+        }
     }
     Ok(o)
+}
+
+/// The map of a projection / goniometric light (ABI 24): the pyramid as MipMap::new built it, un-blocked level by level, and no distribution
+/// (dist_func null, dist_nu = dist_nv = 0: those lights never sample their map); 0xffffffff without a map.
+fn light_map(f: &mut Flat, map: &Option<Arc<MipMap<Spectrum>>>) -> u32 {
+    let m = match map { Some(m) => m, None => return 0xffff_ffff };
+    let mut tex: Vec<f32> = Vec::new();
+    for lvl in &m.pyramid {
+        for t in 0..lvl.v_size() { for s in 0..lvl.u_size() { tex.extend_from_slice(&lvl[(s, t)].c); } }
+    }
+    f.env_texels.push(tex);
+    let tp = f.env_texels.last().unwrap().as_ptr();                                // heap buffer: stable while f lives
+    f.envmaps.push(RsptEnvMap { width: m.width() as u32, height: m.height() as u32, n_levels: m.levels() as u32, pad: 0,
+                                texels: tp, dist_nu: 0, dist_nv: 0, dist_func: std::ptr::null() });
+    (f.envmaps.len() - 1) as u32
 }
 
 /// What `SamplerIntegrator::render` calls first when RSPT_GPU is set.  Ok(()) = Film.pixels hold the finished frame.
