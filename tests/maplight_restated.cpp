@@ -205,7 +205,7 @@ static Spec estimate_direct(View& v, const Interaction& it, const Bsdf& bsdf, P2
             Spec li2;
             Interaction light_isect;
             if (sc.intersect(ray, &light_isect, c)) {
-                const rspt_prim& hp = sc.d.prims[light_isect.prim];
+                const rspt_prim& hp = sc.hit_prim(light_isect);   // (a hit inside an instance under the reference behaviour has lost its primitive: no material, no area light)
                 if (light.kind == RSPT_LIGHT_DIFFUSE_AREA && hp.area_light >= 0 && (uint32_t)hp.area_light == light_num)   // :550-558
                     li2 = light_l(light, light_isect.n, -wi);
             } else
@@ -238,7 +238,7 @@ static Spec path_li(RenderCtx& cx, const Ray& r, Sampler& sampler, Counters* c) 
     for (;;) {
         Interaction isect;
         if (sc.intersect(ray, &isect, c)) {   // :77-81
-            const rspt_prim& hp = sc.d.prims[isect.prim];
+            const rspt_prim& hp = sc.hit_prim(isect);
             if (bounces == 0 || specular_bounce) {   // :97-101, SurfaceInteraction::le (interaction.rs:475-483)
                 if (hp.area_light >= 0) l = l + beta * light_l(v.light(hp.area_light), isect.n, -ray.d);
                 else l = l + beta * Spec();

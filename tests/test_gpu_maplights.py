@@ -1,26 +1,20 @@
 """-m gpu: projection and goniometric lights (ABI 24) in rspt_render under the path integrator, and in rspt_light_distribution.  Every camera
 sample's radiance equals the hand restatement tests/maplight_restated.cpp (held to the oracle's own li on scenes without these lights by
 tests/test_maplight_host.py) bit for bit; a map-less goniometric light is a point light; the power and spatial tables equal the restated ones;
-ao does not see the lights; and what stays out of scope is refused by name."""
+ao does not see the lights; and what stays out of scope is refused by name.  Both shade instantiations these scenes can take are launched and named
+(RSPT_VERBOSE): generic-maplight over the gallery, over textures, static instances, masks, a null surface and an infinite light, and under a lens, a moving camera,
+a crop window with a shard and a sample range; all-maplight over dynamic materials and moving instances, and forced onto the gallery."""
 import numpy as np
 import pytest
 
 from rs_pbrt_amd import abi, scenes
-from tests.test_maplight_host import assert_same_li, build_restated, restated_distribution, restated_render
-from tests.util import film_rmse
+from tests.test_maplight_host import assert_same_li, build_restated, dynamic_rd, feature_rd, moving_rd, restated_distribution, restated_render
+from tests.util import dynamic_maplight_room, film_rmse, light_maps, maplight_feature_room, moving_maplight_room, shade_instantiation
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 LOOK = ((0, 3.0, -6.5), (0, 1.4, 0), (0, 1, 0))
 GONIO_AT = (-1.5, 1.8, 0.5)
-
-
-def light_maps():
-    rng = np.random.default_rng(24)
-    proj = rng.uniform(0.05, 1.0, (8, 16, 3)).astype(F32)
-    proj[::2, ::2] *= F32(0.1)      # a pattern coarser than a pixel: the frame shows it
-    gonio = rng.uniform(0.2, 1.0, (4, 8, 3)).astype(F32)
-    return proj, gonio
 
 
 def gonio_to_world():
@@ -81,6 +75,13 @@ def parity(gpu, restated, sc, rd, rmse=1e-5):
     return li
 
 
+def parity_on(gpu, restated, sc, rd, monkeypatch, capfd, kernel):
+    """parity() by the shade instantiation named `kernel`: a scene that quietly takes another one fails"""
+    li, name = shade_instantiation(monkeypatch, capfd, lambda: parity(gpu, restated, sc, rd))
+    assert name == kernel
+    return li
+
+
 def test_the_gallery_holds_what_it_says(gallery_scene, restated):
     """the geometry the parity cases rely on, from the restated light functions: the projector's frustum edge and back half-space, the goniometric
     light's poles and seam all fall on surfaces the camera sees"""
@@ -115,11 +116,82 @@ def test_the_gallery_holds_what_it_says(gallery_scene, restated):
 
 @pytest.mark.parametrize("sampler,strategy,depth,batch", [("sobol", abi.LIGHTS_SPATIAL, 7, None), ("halton", abi.LIGHTS_POWER, 5, None),
                                                           ("sobol", abi.LIGHTS_UNIFORM, 3, None), ("sobol", abi.LIGHTS_SPATIAL, 7, 2048)])
-def test_gallery_li_equals_restated_li(gpu, restated, gallery_scene, monkeypatch, sampler, strategy, depth, batch):
+def test_gallery_li_equals_restated_li(gpu, restated, gallery_scene, monkeypatch, capfd, sampler, strategy, depth, batch):
     if batch:
         monkeypatch.setenv("RSPT_BATCH", str(batch))      # 48 x 36 x 4 samples in several batches
     rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=depth, sampler=sampler, light_strategy=strategy)
-    li = parity(gpu, restated, gallery_scene, rd)
+    li = parity_on(gpu, restated, gallery_scene, rd, monkeypatch, capfd, "generic-maplight")
+    assert np.nanmean(li) > 0.0
+
+
+# ---- the all-features instantiation (256 VGPRs, one wave per SIMD): a map light next to a dynamic material or a moving instance ----
+@pytest.mark.parametrize("sampler,strategy,depth,batch", [("sobol", abi.LIGHTS_SPATIAL, 5, None), ("halton", abi.LIGHTS_POWER, 7, None),      # (depth 7: past the roulette threshold)
+                                                          ("sobol", abi.LIGHTS_SPATIAL, 5, 2048)])
+def test_dynamic_materials_under_map_lights(gpu, restated, monkeypatch, capfd, sampler, strategy, depth, batch):
+    """eight materials whose lobe lists are built per hit under a mapped projection light, a mapped and a map-less goniometric light and an area light; with
+    RSPT_BATCH the one-wave kernel runs over several batches"""
+    if batch:
+        monkeypatch.setenv("RSPT_BATCH", str(batch))
+    sc = dynamic_maplight_room(gpu.bvh_build)
+    li = parity_on(gpu, restated, sc, dynamic_rd(sampler, strategy, depth), monkeypatch, capfd, "all-maplight")
+    assert np.nanmean(li) > 0.0
+
+
+@pytest.mark.parametrize("mode,dynamic", [("fixed", False), ("reference", False), ("fixed", True)])
+def test_moving_instances_under_map_lights(gpu, restated, monkeypatch, capfd, mode, dynamic):
+    """moving, turning and static instances of a textured pyramid (shutter 0 .. 1), both instancing behaviours; and next to a dynamic material, which Sobol' serves"""
+    sc = moving_maplight_room(gpu.bvh_build, mode, dynamic)
+    assert int(sc.instances["animated"].sum()) >= 5
+    li = parity_on(gpu, restated, sc, moving_rd(), monkeypatch, capfd, "all-maplight")
+    assert np.nanmean(li) > 0.0
+
+
+def test_all_maplight_forced_on_the_gallery(gpu, restated, gallery_scene, monkeypatch, capfd):
+    """RSPT_SHADE_VARIANT=all-maplight on a scene the generic set serves: the same bits as the default render, and as the restated li — the big instantiation
+    computes nothing else, whatever a new scene does"""
+    rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=6)
+    default = parity_on(gpu, restated, gallery_scene, rd, monkeypatch, capfd, "generic-maplight")
+    monkeypatch.setenv("RSPT_SHADE_VARIANT", "all-maplight")
+    forced = parity_on(gpu, restated, gallery_scene, rd, monkeypatch, capfd, "all-maplight")
+    assert_same_li(forced, default)
+
+
+# ---- the generic map-light instantiation over what its gallery lacks ----
+@pytest.fixture(scope="module")
+def feature_scene(gpu):
+    return maplight_feature_room(gpu.bvh_build)
+
+
+@pytest.mark.parametrize("sampler", ["sobol", "halton"])
+def test_feature_room_li_equals_restated_li(gpu, restated, feature_scene, monkeypatch, capfd, sampler):
+    """the texture stage, bump, static instances, a null surface in the beam, alpha and shadow-alpha masks, a medium interface, and the map lights' maps behind
+    an infinite light's in the pool (envmap indices 1 and 2)"""
+    li = parity_on(gpu, restated, feature_scene, feature_rd(sampler), monkeypatch, capfd, "generic-maplight")
+    assert np.nanmean(li) > 0.0
+
+
+def test_feature_room_light_distributions_equal_the_restated_tables(gpu, restated, feature_scene):
+    """the map-light table kernels over an infinite light's power and sample_li too"""
+    sc = feature_scene
+    lo, hi = sc.nodes["bmin"][0], sc.nodes["bmax"][0]
+    pts = np.random.default_rng(6).uniform(lo - 0.5, hi + 0.5, (20, 3)).astype(F32)
+    with gpu.DeviceScene(sc) as ds:
+        f, c, _, _ = gpu.light_distribution(ds, abi.LIGHTS_POWER, pts[0])
+        wf, wc, _, _ = restated_distribution(restated, sc, abi.LIGHTS_POWER, pts[0])
+        assert np.array_equal(f.view(np.uint32), wf.view(np.uint32)) and np.array_equal(c.view(np.uint32), wc.view(np.uint32)) and f.min() > 0
+        for p in pts:
+            f, c, nv, vx = gpu.light_distribution(ds, abi.LIGHTS_SPATIAL, p)
+            wf, wc, wnv, wvx = restated_distribution(restated, sc, abi.LIGHTS_SPATIAL, p)
+            assert list(nv) == list(wnv) and list(vx) == list(wvx)
+            assert np.array_equal(f.view(np.uint32), wf.view(np.uint32)) and np.array_equal(c.view(np.uint32), wc.view(np.uint32)), p
+
+
+# ---- the render description's features over map lights ----
+@pytest.mark.parametrize("kw", [dict(lens_radius=0.05, focal_distance=6.0), dict(look_at_end=((0.6, 3.2, -6.2), (0.2, 1.4, 0), (0, 1, 0))),
+                                dict(crop=(0.1, 0.85, 0.2, 0.95), shard=(1, 3, 2), sample_range=(1, 2))], ids=["lens", "moving-camera", "crop-shard-range"])
+def test_gallery_under_render_features(gpu, restated, gallery_scene, monkeypatch, capfd, kw):
+    rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=5, **kw)
+    li = parity_on(gpu, restated, gallery_scene, rd, monkeypatch, capfd, "generic-maplight")
     assert np.nanmean(li) > 0.0
 
 

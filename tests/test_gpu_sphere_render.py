@@ -1,37 +1,20 @@
 """-m gpu: analytic spheres as surfaces in rspt_render — the path and AO integrators under Sobol' and Halton.  Every camera sample's radiance
 equals a hand restatement of PathIntegrator::li / AOIntegrator::li over a scene view that intersects spheres (tests/sphere_render_restated.cpp,
 held to the oracle's own li on triangle scenes by tests/test_sphere_render_host.py) bit for bit; a sphere no ray reaches changes nothing; a
-sphere casts its analytic shadow; a furnace sphere returns its albedo; and what stays out of scope is refused."""
+sphere casts its analytic shadow; a furnace sphere returns its albedo; and what stays out of scope is refused.  Both sphere instantiations of the shade
+stage are launched and named (RSPT_VERBOSE): generic-sphere by the gallery, dynamic-sphere by a room of dynamic materials and forced onto the gallery."""
 import math
 
 import numpy as np
 import pytest
 
 from rs_pbrt_amd import abi, scenes
-from tests.test_sphere_render_host import assert_same_li, build_restated, restated_render
-from tests.util import film_rmse, texture_image
+from tests.test_sphere_render_host import assert_same_li, build_restated, dynamic_sphere_rd, restated_render
+from tests.util import dynamic_sphere_room, film_rmse, shade_instantiation, texture_image, xf
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 LOOK = ((0, 2.2, -6.5), (0, 1.0, 0), (0, 1, 0))
-
-
-def rot(axis, deg):
-    a = math.radians(deg)
-    c, s = math.cos(a), math.sin(a)
-    x, y, z = np.asarray(axis, float) / np.linalg.norm(axis)
-    m = np.eye(4)
-    m[:3, :3] = [[c + x * x * (1 - c), x * y * (1 - c) - z * s, x * z * (1 - c) + y * s],
-                 [y * x * (1 - c) + z * s, c + y * y * (1 - c), y * z * (1 - c) - x * s],
-                 [z * x * (1 - c) - y * s, z * y * (1 - c) + x * s, c + z * z * (1 - c)]]
-    return m
-
-
-def xf(t, axis=(0, 1, 0), deg=0.0, scale=(1, 1, 1)):
-    m = rot(axis, deg)
-    m[:3, :3] = m[:3, :3] @ np.diag(scale)
-    m[:3, 3] = t
-    return scenes.Transform(m.astype(F32))
 
 
 def sphere_gallery(builder, lights="all", camera_inside=False):
@@ -99,18 +82,51 @@ def parity(gpu, restated, sc, rd, rmse=1e-5):
     return li
 
 
+def parity_on(gpu, restated, sc, rd, monkeypatch, capfd, kernel):
+    """parity() by the shade instantiation named `kernel`: a scene that quietly takes another one fails"""
+    li, name = shade_instantiation(monkeypatch, capfd, lambda: parity(gpu, restated, sc, rd))
+    assert name == kernel
+    return li
+
+
 CASES = [("all", "sobol", "path", abi.LIGHTS_SPATIAL, 7), ("all", "halton", "path", abi.LIGHTS_POWER, 5), ("delta", "sobol", "path", abi.LIGHTS_UNIFORM, 3),
          ("area", "halton", "path", abi.LIGHTS_SPATIAL, 9), ("sky", "sobol", "path", abi.LIGHTS_POWER, 6),
          ("all", "sobol", "ao", abi.LIGHTS_SPATIAL, 5), ("all", "halton", "ao", abi.LIGHTS_SPATIAL, 5)]
 
 
 @pytest.mark.parametrize("lights,sampler,integrator,strategy,depth", CASES)
-def test_sphere_gallery_li_equals_restated_li(gpu, restated, lights, sampler, integrator, strategy, depth):
+def test_sphere_gallery_li_equals_restated_li(gpu, restated, monkeypatch, capfd, lights, sampler, integrator, strategy, depth):
     sc = sphere_gallery(gpu.bvh_build, lights)
     assert (sc.prims["mesh"] == abi.MESH_SPHERE).sum() == 13
     rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=depth, sampler=sampler, integrator=integrator, light_strategy=strategy, ao_samples=4)
-    li = parity(gpu, restated, sc, rd)
+    if integrator == "path":
+        li = parity_on(gpu, restated, sc, rd, monkeypatch, capfd, "generic-sphere")
+    else:   # (ao has its own kernel: the shade stage does not run)
+        li = parity(gpu, restated, sc, rd)
     assert np.nanmean(li) > 0.0
+
+
+# ---- the dynamic sphere instantiation (256 VGPRs + scratch, one wave per SIMD): a sphere scene with a lobe list built per hit ----
+@pytest.mark.parametrize("sampler,strategy,depth,batch", [("sobol", abi.LIGHTS_SPATIAL, 6, None), ("halton", abi.LIGHTS_POWER, 5, None), ("sobol", abi.LIGHTS_SPATIAL, 6, 2048)])
+def test_dynamic_materials_on_spheres(gpu, restated, monkeypatch, capfd, sampler, strategy, depth, batch):
+    """seven dynamic recipes on full, z-clipped, phi-clipped and mirror-scaled spheres (UV and spherical mappings) and an eighth on a triangle slab; with
+    RSPT_BATCH the one-wave kernel runs over several batches"""
+    if batch:
+        monkeypatch.setenv("RSPT_BATCH", str(batch))
+    sc = dynamic_sphere_room(gpu.bvh_build)
+    assert (sc.prims["mesh"] == abi.MESH_SPHERE).sum() == 7
+    li = parity_on(gpu, restated, sc, dynamic_sphere_rd(sampler, strategy, depth), monkeypatch, capfd, "dynamic-sphere")
+    assert np.nanmean(li) > 0.0
+
+
+def test_dynamic_sphere_forced_on_the_gallery(gpu, restated, monkeypatch, capfd):
+    """RSPT_SHADE_VARIANT=dynamic-sphere on a scene the generic sphere set serves: the same bits as the default render"""
+    sc = sphere_gallery(gpu.bvh_build, "all")
+    rd = scenes.make_render_desc(48, 36, 4, LOOK, 60, max_depth=6)
+    default = parity_on(gpu, restated, sc, rd, monkeypatch, capfd, "generic-sphere")
+    monkeypatch.setenv("RSPT_SHADE_VARIANT", "dynamic-sphere")
+    forced = parity_on(gpu, restated, sc, rd, monkeypatch, capfd, "dynamic-sphere")
+    assert_same_li(forced, default)
 
 
 def test_camera_inside_a_sphere(gpu, restated):

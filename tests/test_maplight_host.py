@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from rs_pbrt_amd import abi, scenes
-from tests.util import GALLERY_LOOK_AT, gallery
+from tests.util import DYNAMIC_LOOK_AT, GALLERY_LOOK_AT, MAPLIGHT_LOOK_AT, dynamic_maplight_room, gallery, maplight_feature_room, moving_maplight_room
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
@@ -248,3 +248,78 @@ def test_goniometric_builder_record(t, deg, shape):
     assert np.array_equal(lt["p"][3:12], l2w.m_inv[:3, :3].reshape(-1))
     assert np.allclose(bare["p"][3:12], lt["p"][3:12], atol=1e-6)      # (Matrix4x4::inverse of the product against the product of the inverses)
     assert not lt["p"][12:].any() and sb.envmaps[0]["dist_func"] is None
+
+
+# ---- the rooms that reach the all-features map-light instantiation, and what the generic one's gallery lacks (tests/test_gpu_maplights.py) ----
+def changed(a, b):
+    """the fraction of camera samples whose radiance differs in any bit"""
+    return float((a.view(np.uint32) != b.view(np.uint32)).any(axis=-1).mean())
+
+
+def dynamic_rd(sampler="sobol", strategy=abi.LIGHTS_SPATIAL, depth=5):
+    return scenes.make_render_desc(48, 36, 4, DYNAMIC_LOOK_AT, 75.0, max_depth=depth, sampler=sampler, light_strategy=strategy)
+
+
+def moving_rd(sampler="sobol"):
+    from tests.test_instancing import LOOK
+    return scenes.make_render_desc(48, 36, 4, LOOK, 40.0, shutter=(0.0, 1.0), sampler=sampler)
+
+
+def feature_rd(sampler="sobol"):
+    return scenes.make_render_desc(48, 36, 4, MAPLIGHT_LOOK_AT, 60, max_depth=5, sampler=sampler)
+
+
+@pytest.mark.parametrize("sampler,strategy,depth", [("sobol", abi.LIGHTS_SPATIAL, 5), ("halton", abi.LIGHTS_POWER, 7)])
+def test_restated_li_equals_the_oracles_over_dynamic_materials(restated, oracle, sampler, strategy, depth):
+    """the room of dynamic slabs without its map lights: lobe lists built per hit pass through the restatement unchanged"""
+    from rs_pbrt_amd import lib
+    sc = dynamic_maplight_room(oracle.bvh_build, maplights=False)
+    assert sum(lib.material_lobes(sc, i)[2] is None for i in range(int(sc.desc.n_materials))) >= 8
+    assert check(restated, oracle, sc, dynamic_rd(sampler, strategy, depth)).mean() > 0.0
+
+
+def test_map_lights_reach_the_dynamic_slabs(restated, oracle):
+    """what the GPU case is worth: removing the three map lights changes at least half of the camera samples"""
+    rd = dynamic_rd()
+    lit = dynamic_maplight_room(oracle.bvh_build)
+    kinds = list(lit.lights["kind"])
+    assert kinds.count(abi.LIGHT_PROJECTION) == 1 and kinds.count(abi.LIGHT_GONIOMETRIC) == 2 and kinds.count(abi.LIGHT_DIFFUSE_AREA) == 1
+    with_lights = restated_render(restated, lit, rd)[1]
+    without = restated_render(restated, dynamic_maplight_room(oracle.bvh_build, maplights=False), rd)[1]
+    assert not np.isnan(with_lights).any() and changed(with_lights, without) >= 0.5
+
+
+@pytest.mark.parametrize("mode,dynamic", [("fixed", False), ("reference", False), ("fixed", True)])
+def test_restated_li_equals_the_oracles_over_moving_instances(restated, oracle, mode, dynamic):
+    """the room of moving instances without its map lights, and what they add: at least half of the camera samples"""
+    rd = moving_rd()
+    sc = moving_maplight_room(oracle.bvh_build, mode, dynamic, maplights=False)
+    assert int(sc.instances["animated"].sum()) >= 5
+    without = check(restated, oracle, sc, rd)
+    with_lights = restated_render(restated, moving_maplight_room(oracle.bvh_build, mode, dynamic), rd)[1]
+    assert not np.isnan(with_lights).any() and changed(with_lights, without) >= 0.5
+
+
+@pytest.mark.parametrize("sampler", ["sobol", "halton"])
+def test_restated_li_equals_the_oracles_in_the_feature_room(restated, oracle, sampler):
+    """textures and bump, static instances, a null surface, alpha and shadow-alpha masks, a medium interface and an image-mapped infinite light, without the
+    map lights"""
+    sc = maplight_feature_room(oracle.bvh_build, maplights=False)
+    assert len(sc.instances) == 2 and not sc.instances["animated"].any() and len(sc.media) == 1 and ((sc.prims["material"] == abi.NO_MATERIAL) & (sc.prims["mesh"] != abi.MESH_INSTANCE)).sum() == 2
+    assert (np.asarray(sc.meshes["alpha_tex"]) != 0).sum() == 1 and (np.asarray(sc.meshes["shadow_alpha_tex"]) != 0).sum() == 1
+    assert check(restated, oracle, sc, feature_rd(sampler)).mean() > 0.0
+
+
+def test_the_feature_room_holds_what_it_says(restated, oracle):
+    """the map lights' maps come after the infinite light's (prim >= 1; only that one carries a distribution), no material is dynamic (the generic set serves
+    the room), and the two masks shape what the camera sees: making them opaque changes at least 5 % of the camera samples"""
+    from rs_pbrt_amd import lib
+    rd = feature_rd()
+    sc = maplight_feature_room(oracle.bvh_build)
+    by_kind = {int(k): int(p) for k, p in zip(sc.lights["kind"], sc.lights["prim"])}
+    assert by_kind[abi.LIGHT_INFINITE] == 0 and by_kind[abi.LIGHT_PROJECTION] == 1 and by_kind[abi.LIGHT_GONIOMETRIC] == 2
+    assert [e["dist_func"] is not None for e in sc.envmaps] == [True, False, False]
+    assert all(lib.material_lobes(sc, i)[2] is not None for i in range(int(sc.desc.n_materials)))
+    masked = restated_render(restated, sc, rd)[1]
+    opaque = restated_render(restated, maplight_feature_room(oracle.bvh_build, masks=False), rd)[1]
+    assert not np.isnan(masked).any() and changed(masked, opaque) >= 0.05

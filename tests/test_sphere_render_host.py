@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from rs_pbrt_amd import abi, scenes
-from tests.util import GALLERY_LOOK_AT, TEXTURED_LOOK_AT, gallery, random_scene, sky_scene, textured_room
+from tests.util import GALLERY_LOOK_AT, SPHERE_LOOK_AT, TEXTURED_LOOK_AT, dynamic_sphere_room, gallery, random_scene, sky_scene, textured_room
 from tests.test_alpha_masks import masked_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,3 +101,35 @@ def test_restated_ao_li_equals_the_oracles(restated, oracle, cos_sample):
     for sampler in ("sobol", "halton"):
         rd = scenes.cornell_render_desc(res=32, spp=4, integrator="ao", ao_samples=4, ao_cos_sample=cos_sample, sampler=sampler)
         check(restated, oracle, sc, rd)
+
+
+# ---- the room that reaches the dynamic sphere instantiation (tests/test_gpu_sphere_render.py) ----
+def dynamic_sphere_rd(sampler="sobol", strategy=abi.LIGHTS_SPATIAL, depth=6):
+    return scenes.make_render_desc(48, 36, 4, SPHERE_LOOK_AT, 60, max_depth=depth, sampler=sampler, light_strategy=strategy)
+
+
+@pytest.mark.parametrize("sampler,strategy,depth", [("sobol", abi.LIGHTS_SPATIAL, 6), ("halton", abi.LIGHTS_POWER, 5)])
+def test_restated_li_equals_the_oracles_on_the_dynamic_rooms_triangle_twin(restated, oracle, sampler, strategy, depth):
+    """the oracle has no spheres: the same dynamic materials (lobe lists built per hit, UV and spherical mappings) on slabs pass through the restatement unchanged"""
+    from rs_pbrt_amd import lib
+    sc = dynamic_sphere_room(oracle.bvh_build, shapes="slabs")
+    assert len(sc.spheres) == 0 and sum(lib.material_lobes(sc, i)[2] is None for i in range(int(sc.desc.n_materials))) >= 7
+    assert check(restated, oracle, sc, dynamic_sphere_rd(sampler, strategy, depth)).mean() > 0.0
+
+
+def test_dynamic_materials_fill_the_sphere_room(restated):
+    """what the GPU case is worth: at least seven materials are dynamic, seven spheres (full, z-clipped, phi-clipped, mirror-scaled) and a slab carry them, and a
+    constant matte in their place changes at least 20 % of the camera samples"""
+    from rs_pbrt_amd import lib
+    rd = dynamic_sphere_rd()
+    sc = dynamic_sphere_room(lib.bvh_build)
+    dyn = [i for i in range(int(sc.desc.n_materials)) if lib.material_lobes(sc, i)[2] is None]
+    assert len(dyn) >= 7
+    on_spheres = set(int(m) for m in sc.prims["material"][sc.prims["mesh"] == abi.MESH_SPHERE])
+    on_tris = set(int(m) for m in sc.prims["material"][sc.prims["mesh"] != abi.MESH_SPHERE])
+    assert len(sc.spheres) == 7 and len(on_spheres & set(dyn)) == 7 and on_tris & set(dyn)
+    assert int(sc.spheres["transform_swaps_handedness"].sum()) == 1 and (sc.spheres["phi_max"] < 6.0).sum() == 2 and (sc.spheres["z_max"] < sc.spheres["radius"]).sum() == 2
+    li = restated_render(restated, sc, rd)[1]
+    plain = restated_render(restated, dynamic_sphere_room(lib.bvh_build, dynamic=False), rd)[1]
+    assert not np.isnan(li).any()
+    assert float((li.view(np.uint32) != plain.view(np.uint32)).any(axis=-1).mean()) >= 0.2
