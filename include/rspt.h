@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 24
+#define RSPT_ABI_VERSION 25
 
 /* error codes */
 #define RSPT_OK 0
@@ -499,7 +499,22 @@ typedef struct {
     uint32_t camera_animated;
     float camera_to_world_end[16];
     float camera_time[2];
+    /* ABI 25: which Camera::generate_ray_differential makes the camera rays (src/core/camera.rs; RSPT_CAMERA_*, below).  0 is the perspective camera, so a
+     * zero-filled description means what it meant before.  All three are served wherever the perspective camera is: the five integrators, the six samplers,
+     * a moving camera, crop / shard / sample range.  What each kind reads:
+     *   PERSPECTIVE  (src/cameras/perspective.rs:190-280)  raster_to_camera, lens_radius, focal_distance, the shutter, camera_to_world with its animation.
+     *   ORTHOGRAPHIC (src/cameras/orthographic.rs:150-235) raster_to_camera as OrthographicCamera::new builds it (inverse(orthographic(0, 1)) * raster_to_screen),
+     *                lens_radius, focal_distance, the shutter, camera_to_world with its animation.  Rays start ON the film plane (o = raster_to_camera(p_film),
+     *                d = (0, 0, 1)); dx_camera / dy_camera are raster_to_camera's vector transform of the raster axes.  With a lens the library follows the
+     *                reference: the origin becomes the lens point, and both offset rays aim at p_camera + dx_camera + (0, 0, ft) with ft taken from the lens
+     *                ray's own direction (ry == rx).
+     *   ENVIRONMENT  (src/cameras/environment.rs:92-116)   full_res (theta = pi y / full_res[1], phi = 2 pi x / full_res[0], d = (sin theta cos phi,
+     *                cos theta, sin theta sin phi), o = 0), the shutter, camera_to_world with its animation.  raster_to_camera, lens_radius and focal_distance
+     *                are ignored.  Its rays carry NO differentials: textures are looked up as for a bounce ray.
+     * RealisticCamera (lens files, exit-pupil tables) is not served: the caller keeps its CPU loop.  A value above 2 is RSPT_E_INVALID (the text names camera_kind). */
+    uint32_t camera_kind;            /* sits in what was the struct's tail padding (8-byte alignment): sizeof stays 1456 and needs no explicit padding */
 } rspt_render_desc;
+enum { RSPT_CAMERA_PERSPECTIVE = 0, RSPT_CAMERA_ORTHOGRAPHIC = 1, RSPT_CAMERA_ENVIRONMENT = 2 };
 /* RSPT_INTEGRATOR_VOLPATH: VolPathIntegrator::li (src/integrators/volpath.rs:60-347) with max_depth, rr_threshold and
  * light_strategy as for "path" (api.rs:350-380).  Camera rays start outside every medium (make_camera passes
  * MediumInterface::default().outside, api.rs:1638-1645).  As in v0.9.12: the BSDF- / phase-sampled half of estimate_direct is

@@ -4,7 +4,7 @@ Every struct here must stay byte-compatible with the header; tests/test_abi.py c
 sizes against the values the library reports."""
 import ctypes as C
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 OK, E_INVALID, E_NODEVICE, E_HIP, E_UNSUPPORTED, E_NOMEM, E_PEER = 0, -1, -2, -3, -4, -5, -6
 
@@ -20,6 +20,7 @@ INTEGRATOR_PATH, INTEGRATOR_AO, INTEGRATOR_DIRECT, INTEGRATOR_VOLPATH, INTEGRATO
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
 DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_UNIFORM, LIGHTS_POWER, LIGHTS_SPATIAL = 0, 1, 2
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT = 0, 1, 2      # ABI 25: rspt_render_desc.camera_kind (0 = what a zero-filled desc always meant)
 TEX_CONSTANT, TEX_IMAGE, TEX_SCALE, TEX_MIX, TEX_CHECKERBOARD, TEX_DOTS, TEX_FBM, TEX_MARBLE, TEX_WINDY, TEX_WRINKLED = range(1, 11)
 MAP_UV, MAP_PLANAR, MAP_SPHERICAL, MAP_CYLINDRICAL, MAP_IDENTITY3D = 1, 2, 3, 4, 5
 WRAP_REPEAT, WRAP_BLACK, WRAP_CLAMP = 0, 1, 2
@@ -134,7 +135,8 @@ class RenderDesc(C.Structure):
                 ("direct_strategy", C.c_uint32), ("pixel_dimensions", C.c_uint32), ("n_light_samples", C.c_void_p),
                 ("strat_x", C.c_uint32), ("strat_y", C.c_uint32), ("strat_jitter", C.c_uint32), ("allow_slow_paths", C.c_uint32), ("maxmin_c_pixel", C.c_void_p),
                 ("sample_begin", C.c_uint64), ("sample_count", C.c_uint64),
-                ("camera_animated", C.c_uint32), ("camera_to_world_end", C.c_float * 16), ("camera_time", C.c_float * 2)]
+                ("camera_animated", C.c_uint32), ("camera_to_world_end", C.c_float * 16), ("camera_time", C.c_float * 2),
+                ("camera_kind", C.c_uint32)]      # ABI 25: in what was the tail padding, sizeof unchanged
 
 
 class Ray(C.Structure):

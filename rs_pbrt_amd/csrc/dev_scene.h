@@ -153,6 +153,8 @@ struct RenderDev {
     const CamAnim* cam_anim;   // nullptr: camera_to_world holds for every ray (rspt_render_desc.camera_animated = 0, or equal key matrices)
     float raster_to_camera[16], camera_to_world[16];
     float lens_radius, focal_distance, shutter_open, shutter_close;
+    uint32_t camera_kind;      // RSPT_CAMERA_* (ABI 25): the same for every ray of a launch, so the branches on it are scalar
+    int32_t full_res[2];       // Film.full_resolution: the environment camera's angles
     int32_t sample_bounds[4], crop_px[4];
     int32_t resolution, log2_res;  // sobol.rs:46-48
     int64_t spp;
@@ -938,13 +940,47 @@ RDEVN void inst_inverse_at(const SceneDev& sc, const InstDev& in, float time, bo
     *ident = id;
 }
 
+// ---- EnvironmentCamera / OrthographicCamera::generate_ray_differential in camera space (ABI 25), differentials dropped ----
+// Environment (environment.rs:92-107): o = 0, d from the film position's two angles, sin / cos as the host's libm computes them (glibc_libm.h);
+// raster_to_camera, lens_radius and focal_distance are not read.  Not inlined, and handed its four numbers by value: with the four double-precision
+// sin / cos evaluations inside k_raygen that kernel grew from 71 to 77 VGPRs and lost a wave per SIMD (7 -> 6); a reference to the kernel's RenderDev
+// argument would put that whole struct into scratch.
+__device__ __noinline__ f3 environment_camera_dir(float film_x, float film_y, float res_x, float res_y) {
+    const float theta = RSPT_PI * film_y / res_y;
+    const float phi = 2.0f * RSPT_PI * film_x / res_x;
+    const float st = rspt_sinf(theta), ct = rspt_cosf(theta), sp = rspt_sinf(phi), cp = rspt_cosf(phi);
+    return f3{st * cp, ct, st * sp};
+}
+// Orthographic (orthographic.rs:150-185): the ray starts on the film plane and looks along +z; a lens REPLACES the origin by the lens point, so the film
+// position survives only through p_focus.
+RDEV void other_camera_ray(const RenderDev& rd, f2 p_film, f3 p_camera, f3 p_lens, f3* o_out, f3* d_out) {
+    if (rd.camera_kind == RSPT_CAMERA_ORTHOGRAPHIC) {
+        f3 o = p_camera, d{0.0f, 0.0f, 1.0f};
+        if (rd.lens_radius > 0.0f) {
+            f2 pl = concentric_disk(f2{p_lens.x, p_lens.y});
+            pl = f2{pl.x * rd.lens_radius, pl.y * rd.lens_radius};
+            float ft = rd.focal_distance / d.z;
+            f3 p_focus = o + d * ft;
+            o = f3{pl.x, pl.y, 0.0f};
+            d = normalize(p_focus - o);
+        }
+        *o_out = o; *d_out = d;
+    } else {
+        *o_out = f3{0.0f, 0.0f, 0.0f};
+        *d_out = environment_camera_dir(p_film.x, p_film.y, (float)rd.full_res[0], (float)rd.full_res[1]);
+    }
+}
+
 // ---- PerspectiveCamera::generate_ray_differential (perspective.rs:190-280), differentials dropped ----
 // p_lens: (CameraSample.p_lens, CameraSample.time) — the time value matters to a moving camera only
+// rd.camera_kind (ABI 25) is a kernel argument: one scalar branch sends the other two cameras to other_camera_ray (the orthographic camera's o is p_camera); the Transform::transform_ray tail is shared
 RDEV void camera_ray(const RenderDev& rd, f2 p_film, f3 p_lens, f3* o_out, f3* d_out, float* tmax_out) {
     f3 p_camera = xf_point(rd.raster_to_camera, f3{p_film.x, p_film.y, 0.0f});
     f3 o{0.0f, 0.0f, 0.0f}, d = normalize(p_camera);
     float c2w[16];
     camera_to_world_at(rd, p_lens.z, c2w);
+    if (rd.camera_kind != RSPT_CAMERA_PERSPECTIVE) other_camera_ray(rd, p_film, p_camera, p_lens, &o, &d);
+    else
     if (rd.lens_radius > 0.0f) {
         f2 pl = concentric_disk(f2{p_lens.x, p_lens.y});
         pl = f2{pl.x * rd.lens_radius, pl.y * rd.lens_radius};

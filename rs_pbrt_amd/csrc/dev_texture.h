@@ -507,6 +507,10 @@ RDEVN void compute_differentials(const TexHit& h, f3 rx_o, f3 rx_d, f3 ry_o, f3 
 
 // PerspectiveCamera::generate_ray_differential's offset rays (perspective.rs:205-220, 245-271), transformed
 // (transform.rs:550-556) and scaled by 1 / sqrt(spp) (integrator.rs:140-144; geometry.rs:2398-2405)
+// The orthographic camera (ABI 25; a scalar branch on rd.camera_kind) takes its arm: dx_camera / dy_camera are raster_to_camera's VECTOR transform of the
+// raster axes (orthographic.rs:73-82); without a lens the offset rays start one pixel over and keep the ray's direction (:218-226); with one, both start at
+// the lens point and aim at p_camera + dx_camera + (0, 0, ft), ft from the lens ray's own direction — dy_camera is unused, ry == rx (:187-217).  The
+// environment camera has no differentials and never comes here (kernels.h texture_slot, dl_serial.h).
 RDEVN void camera_differentials(const RenderDev& rd, f2 p_film, f3 p_lens, f3 ray_o, f3 ray_d, f3* rx_o, f3* rx_d, f3* ry_o, f3* ry_d) {
     float c2w[16];
     camera_to_world_at(rd, p_lens.z, c2w);   // the matrix the ray itself was transformed with (Transform::transform_ray, transform.rs:550-556)
@@ -516,6 +520,26 @@ RDEVN void camera_differentials(const RenderDev& rd, f2 p_film, f3 p_lens, f3 ra
     f3 dy_camera = xf_point(rd.raster_to_camera, f3{0.0f, 1.0f, 0.0f}) - c0;
     f3 ox{0.0f, 0.0f, 0.0f}, oy = ox;
     f3 dx = normalize(p_camera + dx_camera), dy = normalize(p_camera + dy_camera);
+    if (rd.camera_kind == RSPT_CAMERA_ORTHOGRAPHIC) {
+        dx_camera = xf_vector(rd.raster_to_camera, f3{1.0f, 0.0f, 0.0f});
+        dy_camera = xf_vector(rd.raster_to_camera, f3{0.0f, 1.0f, 0.0f});
+        f3 o = p_camera, d{0.0f, 0.0f, 1.0f};
+        if (rd.lens_radius > 0.0f) {
+            f2 pl = concentric_disk(f2{p_lens.x, p_lens.y});
+            pl = f2{pl.x * rd.lens_radius, pl.y * rd.lens_radius};
+            float ft = rd.focal_distance / d.z;
+            f3 p_focus = o + d * ft;
+            o = f3{pl.x, pl.y, 0.0f};
+            d = normalize(p_focus - o);
+            ft = rd.focal_distance / d.z;
+            p_focus = p_camera + dx_camera + f3{0.0f, 0.0f, 1.0f} * ft;
+            ox = oy = o;
+            dx = dy = normalize(p_focus - o);
+        } else {
+            ox = o + dx_camera; oy = o + dy_camera;
+            dx = dy = d;
+        }
+    } else
     if (rd.lens_radius > 0.0f) {
         f2 pl = concentric_disk(f2{p_lens.x, p_lens.y});
         pl = f2{pl.x * rd.lens_radius, pl.y * rd.lens_radius};

@@ -202,7 +202,7 @@ struct DlSerial {
         rgb ret = mkrgb(0.0f);
         uint32_t walked = 0;
         RayDiff cur{false, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}};   // the differentials of the ray being traced
-        if (tex) { cur.has = true; camera_differentials(base.rd, p_film, p_lens, ray_o, ray_d, &cur.rx_o, &cur.rx_d, &cur.ry_o, &cur.ry_d); }
+        if (tex && base.rd.camera_kind != RSPT_CAMERA_ENVIRONMENT) { cur.has = true; camera_differentials(base.rd, p_film, p_lens, ray_o, ray_d, &cur.rx_o, &cur.rx_d, &cur.ry_o, &cur.ry_d); }
         for (;;) {
             // ---- enter li(ray, depth = sp) ----
             rgb l = mkrgb(0.0f);

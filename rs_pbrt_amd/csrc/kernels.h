@@ -948,7 +948,7 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
     s.p = h.p; s.uv = h.uv;
     s.dudx = s.dvdx = s.dudy = s.dvdy = 0.0f;
     s.dpdx = s.dpdy = f3{0.0f, 0.0f, 0.0f};
-    if (with_diff) {
+    if (with_diff && rd.camera_kind != RSPT_CAMERA_ENVIRONMENT) {   // (the environment camera's rays carry no differentials, environment.rs:100-107: the zeros above, as for a bounce ray)
         const float4* rp = reinterpret_cast<const float4*>(pb.ray_cont + p);
         const float4 r0 = rp[0], r1 = rp[1];
         const float2 pf = pb.p_film[smp];

@@ -64,6 +64,8 @@ struct RenderRun {
 int RenderRun::validate() {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
+    if (d->camera_kind > RSPT_CAMERA_ENVIRONMENT) return fail(RSPT_E_INVALID, "camera_kind %u (0 perspective, 1 orthographic, 2 environment)", d->camera_kind);
+    if (d->camera_kind == RSPT_CAMERA_ENVIRONMENT && (d->full_res[0] <= 0 || d->full_res[1] <= 0)) return fail(RSPT_E_INVALID, "camera_kind environment: full_res must be positive");
     // Analytic spheres are served as surfaces (hit, shaded, textured, blocking light) by the path and AO integrators in their wavefront form
     // (Sobol' / Halton).  Everything else that holds a sphere is refused, so the caller keeps its CPU loop: sphere area lights (their
     // sample_with_ref_point / pdf_with_ref_point and power are not on the device), the directlighting / whitted / volpath forms and the pixel
@@ -167,6 +169,7 @@ int RenderRun::constants() {
     memcpy(rd.raster_to_camera, d->raster_to_camera, sizeof rd.raster_to_camera);
     memcpy(rd.camera_to_world, d->camera_to_world, sizeof rd.camera_to_world);
     rd.lens_radius = d->lens_radius; rd.focal_distance = d->focal_distance;
+    rd.camera_kind = d->camera_kind; rd.full_res[0] = d->full_res[0]; rd.full_res[1] = d->full_res[1];
     rd.cam_anim = nullptr;
     if (d->camera_animated) {   // AnimatedTransform::new (camera_anim.h); equal key matrices = a camera that does not move
         CamAnim ca;

@@ -200,6 +200,11 @@ class Transform:
         return Transform(np.eye(4, dtype=F32), np.eye(4, dtype=F32))
 
     @staticmethod
+    def orthographic(z_near, z_far):  # transform.rs:452-460
+        n, f = F32(z_near), F32(z_far)
+        return Transform.scale(1, 1, F32(1) / (f - n)) * Transform.translate((0, 0, -n))
+
+    @staticmethod
     def perspective(fov, n, f):  # transform.rs:461-489
         n, f = F32(n), F32(f)
         persp = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, f / (f - n), -f * n / (f - n)], [0, 0, 1, 0]], F32)
@@ -1135,8 +1140,11 @@ def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.
                      focal_distance=1e6, max_sample_luminance=float("inf"), shard=(0, 1, 64), sampler="sobol",
                      sample_at_pixel_center=False, integrator="path", ao_samples=64, ao_cos_sample=True, direct_strategy="all", light_samples=None,
                      dimensions=4, strat=(4, 4), jitter=True, sample_range=None, allow_slow_paths=True, look_at_end=None, camera_times=(0.0, 1.0),
-                     shutter=(0.0, 1.0), mirror_x=False):
-    """allow_slow_paths: True here (tests and bench want the device path whatever its speed); the Rust shim passes 0, so that a pixel-sampler
+                     shutter=(0.0, 1.0), mirror_x=False, camera="perspective", screen_window=None):
+    """camera: "perspective" | "orthographic" | "environment" (rspt_render_desc.camera_kind, ABI 25).  `fov` is read by the perspective camera only;
+    screen_window (x0, x1, y0, y1) is the "screenwindow" parameter, default that of the cameras' create() (the frame's aspect ratio around 0); the
+    environment camera reads neither, nor the lens.
+    allow_slow_paths: True here (tests and bench want the device path whatever its speed); the Rust shim passes 0, so that a pixel-sampler
     frame of few tiles — which the device renders slower than the host's tile loop — comes back as RSPT_E_UNSUPPORTED (include/rspt.h)"""
     rd = abi.RenderDesc()
     rd.allow_slow_paths = int(bool(allow_slow_paths))
@@ -1168,7 +1176,12 @@ def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.
         sw = (-frame, frame, F32(-1), F32(1))
     else:
         sw = (F32(-1), F32(1), F32(-1) / frame, F32(1) / frame)
-    cam2screen = Transform.perspective(fov, 1e-2, 1000.0)
+    if screen_window is not None:
+        sw = tuple(F32(v) for v in screen_window)
+    rd.camera_kind = {"perspective": abi.CAMERA_PERSPECTIVE, "orthographic": abi.CAMERA_ORTHOGRAPHIC, "environment": abi.CAMERA_ENVIRONMENT}[camera]
+    # OrthographicCamera::new orthographic.rs:50-70: camera_to_screen = Transform::orthographic(0, 1); the rest is the ProjectiveCamera set-up shared with the
+    # perspective camera.  The environment camera has no projection: the field keeps the perspective matrix, which the library does not read.
+    cam2screen = Transform.orthographic(0.0, 1.0) if camera == "orthographic" else Transform.perspective(fov, 1e-2, 1000.0)
     s2r = Transform.scale(xres, yres, 1) * Transform.scale(F32(1) / (sw[1] - sw[0]), F32(1) / (sw[2] - sw[3]), 1) * Transform.translate((-sw[0], -sw[3], 0))
     r2c = cam2screen.inverse() * s2r.inverse()
     rd.raster_to_camera[:] = r2c.m.reshape(-1).tolist()

@@ -1,10 +1,13 @@
-//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 24) one to one.
+//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 25) one to one.
 //! Uncompiled source for a maintainer (the image this repo is built in has no Rust toolchain); struct layouts are checked
 //! from the C side by tests/test_abi.py, so a mismatch here shows up as a wrong `size_of` against the table in INTEGRATION.md §2.
 #![allow(dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RSPT_ABI_VERSION: c_int = 24;
+pub const RSPT_ABI_VERSION: c_int = 25;
+pub const RSPT_CAMERA_PERSPECTIVE: u32 = 0;   // ABI 25: rspt_render_desc.camera_kind
+pub const RSPT_CAMERA_ORTHOGRAPHIC: u32 = 1;
+pub const RSPT_CAMERA_ENVIRONMENT: u32 = 2;
 pub const RSPT_MESH_INSTANCE: u32 = 0xffff_ffff;
 pub const RSPT_MESH_SPHERE: u32 = 0xffff_fffe;   // ABI 23: v[0] = index into spheres
 pub const RSPT_NO_MATERIAL: u32 = 0xffff_ffff;
@@ -70,6 +73,7 @@ pub struct RsptInstance { pub object: u32, pub to_world: [f32; 16], pub from_wor
     pub strat_x: u32, pub strat_y: u32, pub strat_jitter: u32, pub allow_slow_paths: u32, pub maxmin_c_pixel: *const u32,   // pixel samplers
     pub sample_begin: u64, pub sample_count: u64,   // checkpoint / resume: 0, 0 = the whole frame
     pub camera_animated: u32, pub camera_to_world_end: [f32; 16], pub camera_time: [f32; 2],   // AnimatedTransform camera (transform.rs:894-2124)
+    pub camera_kind: u32,   // ABI 25: RSPT_CAMERA_* (in what was the tail padding: size_of stays 1456)
 }
 #[repr(C)] #[derive(Default)]
 pub struct RsptStats {

@@ -7,7 +7,7 @@
 //! rendered by another integrator than path / ao or with a pixel sampler, comes back Err from rspt_render) under a BVHAccel aggregate, object instances (Primitive::Transformed, static or moving),
 //! matte / plastic / mirror / glass (smooth and rough) / metal / substrate / uber / translucent / mix (handed over as their
 //! parameters — one texture reference each, rspt_material_desc; the library assembles the lobes), diffuse area / point / spot / distant / infinite lights (the light's own MIP
-//! pyramid and Distribution2D image are handed over), homogeneous media, PerspectiveCamera, the Sobol', Halton and the four
+//! pyramid and Distribution2D image are handed over), homogeneous media, PerspectiveCamera / OrthographicCamera / EnvironmentCamera (ABI 25: camera_kind; RealisticCamera is Err), the Sobol', Halton and the four
 //! PCG-backed pixel samplers, the path / ao / directlighting / volpath integrators, any filter (through Film.filter_table).
 //! Image / procedural textures (every class of src/textures/, through Texture::describe of rs_pbrt.patch) go over as texture
 //! graphs wherever a material or mesh refers to one; any parameter may vary over a surface (include/rspt.h: Kd / Ks / roughness
@@ -384,7 +384,22 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
     f.lights = lights;
 
     // ---- camera / film / sampler (perspective.rs:22-43, film.rs:159-173, sobol.rs:15-20, halton.rs:54-78) ----
-    let cam = match &*integ.get_camera() { Camera::Perspective(c) => c.clone_for_shim(), _ => return Err("camera is not perspective".into()) };
+    // ABI 25: the perspective, orthographic and environment cameras are served (rspt_render_desc.camera_kind); each fills the description from its own
+    // fields.  The environment camera has no projection and no lens: the library reads full_res, the shutter and camera_to_world only.
+    struct CamDesc { kind: u32, raster_to_camera: [f32; 16], camera_to_world: crate::core::transform::AnimatedTransform, lens_radius: Float, focal_distance: Float,
+                     shutter_open: Float, shutter_close: Float, film: Arc<crate::core::film::Film> }
+    let cam = match &*integ.get_camera() {
+        Camera::Perspective(c) => { let c = c.clone_for_shim();
+            CamDesc { kind: RSPT_CAMERA_PERSPECTIVE, raster_to_camera: m16(&c.raster_to_camera.m), camera_to_world: c.camera_to_world, lens_radius: c.lens_radius,
+                      focal_distance: c.focal_distance, shutter_open: c.shutter_open, shutter_close: c.shutter_close, film: c.film.clone() } }
+        Camera::Orthographic(c) =>                                                    // orthographic.rs:17-36: pub fields
+            CamDesc { kind: RSPT_CAMERA_ORTHOGRAPHIC, raster_to_camera: m16(&c.raster_to_camera.m), camera_to_world: c.camera_to_world, lens_radius: c.lens_radius,
+                      focal_distance: c.focal_distance, shutter_open: c.shutter_open, shutter_close: c.shutter_close, film: c.film.clone() },
+        Camera::Environment(c) =>                                                     // environment.rs:17-26
+            CamDesc { kind: RSPT_CAMERA_ENVIRONMENT, raster_to_camera: m16(&Transform::default().m), camera_to_world: c.camera_to_world, lens_radius: 0.0,
+                      focal_distance: 0.0, shutter_open: c.shutter_open, shutter_close: c.shutter_close, film: c.film.clone() },
+        Camera::Realistic(_) => return Err("camera is realistic (lens files, exit-pupil tables): not served on the device".into()),
+    };
     // a moving camera goes over as its two key matrices and their times; the library decomposes and interpolates (AnimatedTransform::interpolate)
     let cam_anim = cam.camera_to_world.is_animated();                               // getter: rs_pbrt.patch (actually_animated)
     let film = cam.film.clone();
@@ -414,7 +429,7 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         full_res: [film.full_resolution.x, film.full_resolution.y],
         crop_px: [cb.p_min.x, cb.p_min.y, cb.p_max.x, cb.p_max.y], sample_bounds: [sb.p_min.x, sb.p_min.y, sb.p_max.x, sb.p_max.y],
         filter_radius: [radius.x, radius.y], filter_table, max_sample_luminance: film.max_sample_luminance(),
-        raster_to_camera: m16(&cam.raster_to_camera.m), camera_to_world: m16(&cam.camera_to_world.start_transform().m),
+        raster_to_camera: cam.raster_to_camera, camera_to_world: m16(&cam.camera_to_world.start_transform().m),
         lens_radius: cam.lens_radius, focal_distance: cam.focal_distance, shutter_open: cam.shutter_open, shutter_close: cam.shutter_close,
         sampler_kind, spp, max_depth, rr_threshold,
         light_strategy: match strategy.as_str() { "uniform" => 0, "power" => 1, _ => 2 },    // lightdistrib.rs:393-418 falls back to spatial
@@ -427,6 +442,7 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         sample_begin: 0, sample_count: 0,
         camera_animated: cam_anim as u32, camera_to_world_end: m16(&cam.camera_to_world.end_transform().m),
         camera_time: [cam.camera_to_world.start_time(), cam.camera_to_world.end_time()],
+        camera_kind: cam.kind,
     };
     let sd = RsptSceneDesc {
         nodes: f.nodes.as_ptr(), n_nodes: f.nodes.len() as u64, prims: f.prims.as_ptr(), n_prims: f.prims.len() as u64,
