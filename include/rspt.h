@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 25
+#define RSPT_ABI_VERSION 26
 
 /* error codes */
 #define RSPT_OK 0
@@ -425,6 +425,10 @@ enum { RSPT_SAMPLER_SOBOL = 1,            /* src/samplers/sobol.rs              
 enum { RSPT_LIGHTS_UNIFORM = 0, RSPT_LIGHTS_POWER = 1, RSPT_LIGHTS_SPATIAL = 2 };
                                            /* src/core/lightdistrib.rs:393-418         */
 
+/* One interface of a RealisticCamera's lens system (ABI 26; realistic.rs:27-33 LensElementInterface), metres; curvature_radius 0 = the aperture stop */
+#define RSPT_MAX_LENS_ELEMENTS 32
+typedef struct { float curvature_radius, thickness, eta, aperture_radius; } rspt_lens_element;
+
 /* Everything SamplerIntegrator::render reads from camera, film, sampler and
  * PathIntegrator (integrator.rs:70-100; path.rs:24-34; film.rs:159-173;
  * perspective.rs:22-43; sobol.rs:15-20). */
@@ -500,8 +504,8 @@ typedef struct {
     float camera_to_world_end[16];
     float camera_time[2];
     /* ABI 25: which Camera::generate_ray_differential makes the camera rays (src/core/camera.rs; RSPT_CAMERA_*, below).  0 is the perspective camera, so a
-     * zero-filled description means what it meant before.  All three are served wherever the perspective camera is: the five integrators, the six samplers,
-     * a moving camera, crop / shard / sample range.  What each kind reads:
+     * zero-filled description means what it meant before.  The first three are served wherever the perspective camera is: the five integrators, the six
+     * samplers, a moving camera, crop / shard / sample range.  What each kind reads:
      *   PERSPECTIVE  (src/cameras/perspective.rs:190-280)  raster_to_camera, lens_radius, focal_distance, the shutter, camera_to_world with its animation.
      *   ORTHOGRAPHIC (src/cameras/orthographic.rs:150-235) raster_to_camera as OrthographicCamera::new builds it (inverse(orthographic(0, 1)) * raster_to_screen),
      *                lens_radius, focal_distance, the shutter, camera_to_world with its animation.  Rays start ON the film plane (o = raster_to_camera(p_film),
@@ -511,10 +515,25 @@ typedef struct {
      *   ENVIRONMENT  (src/cameras/environment.rs:92-116)   full_res (theta = pi y / full_res[1], phi = 2 pi x / full_res[0], d = (sin theta cos phi,
      *                cos theta, sin theta sin phi), o = 0), the shutter, camera_to_world with its animation.  raster_to_camera, lens_radius and focal_distance
      *                are ignored.  Its rays carry NO differentials: textures are looked up as for a bounce ray.
-     * RealisticCamera (lens files, exit-pupil tables) is not served: the caller keeps its CPU loop.  A value above 2 is RSPT_E_INVALID (the text names camera_kind). */
-    uint32_t camera_kind;            /* sits in what was the struct's tail padding (8-byte alignment): sizeof stays 1456 and needs no explicit padding */
+     *   REALISTIC    (ABI 26; src/cameras/realistic.rs:198-251, 266-365, 656-735) the lens tables below, film_diagonal, full_res, the shutter, camera_to_world with
+ *                its animation.  raster_to_camera, lens_radius and focal_distance are ignored.  A film sample is traced from the film through every lens
+ *                interface; a sample the lens system vignettes, or whose two shifted rays (the differentials, p_film +- 0.05) are both vignetted in x or in
+ *                y, has ray weight 0: it is added to the film with a contribution of 0 (its filter weight counts), its li in rspt_render_samples is 0 and
+ *                li is never evaluated for it (integrator.rs:149).  Every other sample's contribution is multiplied by its ray weight (film.rs:94-147).
+ *                Served by path and ao under the Sobol' and Halton samplers; volpath, directlighting, whitted and the four pixel samplers answer
+ *                RSPT_E_UNSUPPORTED (the message names the realistic camera), so the caller keeps its CPU loop.
+ * A value above 3 is RSPT_E_INVALID (the text names camera_kind); so is camera_kind 3 with a null or empty lens or bounds table, more than
+ * RSPT_MAX_LENS_ELEMENTS elements, a non-positive full_res or a non-positive film_diagonal. */
+    uint32_t camera_kind;            /* sits in what was ABI 25's tail padding (8-byte alignment) */
+    /* ABI 26, RSPT_CAMERA_REALISTIC only (a zero-filled tail = none of it, as for the other cameras): RealisticCamera::element_interfaces as they stand after
+     * RealisticCamera::new — metres, front to back, the last element's thickness already the focused film distance — and its exit_pupil_bounds,
+     * n x (p_min.x, p_min.y, p_max.x, p_max.y) (the reference makes 64).  rspt_realistic_camera_setup builds both from a lens file's numbers. */
+    const rspt_lens_element* lens_elements; uint32_t n_lens_elements;      /* 1 .. RSPT_MAX_LENS_ELEMENTS */
+    const float* exit_pupil_bounds; uint32_t n_exit_pupil_bounds;
+    float film_diagonal;             /* metres, as Film::diagonal stores it (film.rs:214)           */
+    uint32_t lens_simple_weighting;  /* "simpleweighting" (realistic.rs:245-250)                    */
 } rspt_render_desc;
-enum { RSPT_CAMERA_PERSPECTIVE = 0, RSPT_CAMERA_ORTHOGRAPHIC = 1, RSPT_CAMERA_ENVIRONMENT = 2 };
+enum { RSPT_CAMERA_PERSPECTIVE = 0, RSPT_CAMERA_ORTHOGRAPHIC = 1, RSPT_CAMERA_ENVIRONMENT = 2, RSPT_CAMERA_REALISTIC = 3 };
 /* RSPT_INTEGRATOR_VOLPATH: VolPathIntegrator::li (src/integrators/volpath.rs:60-347) with max_depth, rr_threshold and
  * light_strategy as for "path" (api.rs:350-380).  Camera rays start outside every medium (make_camera passes
  * MediumInterface::default().outside, api.rs:1638-1645).  As in v0.9.12: the BSDF- / phase-sampled half of estimate_direct is
@@ -636,6 +655,23 @@ int rspt_material_lobes(const rspt_scene_desc* desc, uint32_t material, uint32_t
  * rotation quaternions r[2][4] (x, y, z, w; the second one flipped onto the shorter arc), the two scale matrices s[2][16] (row-major; with
  * the key's translation column still in it, transform.rs:2079 — only the 3x3 block is interpolated). */
 int rspt_camera_decompose(const float start_m[16], float start_time, const float end_m[16], float end_time, int32_t* animated_out, float trs_out[46]);
+
+/* Host only (no device, no rspt_init; ABI 26).  Replaces: the part of RealisticCamera::new that builds state (realistic.rs:50-144): lens_data holds the lens
+ * file's numbers, 4 per interface (curvature radius, thickness, eta, aperture diameter; millimetres, front to back, radius 0 = the stop), n_elements of them
+ * (1 .. RSPT_MAX_LENS_ELEMENTS).  elements_out[n_elements] receives the interfaces in metres — a stop takes aperture_diameter_mm unless that exceeds the
+ * file's value, which is then kept (:62-72) — with the last thickness replaced by focus_thick_lens(focus_distance) (:366-499); bounds_out[4 n_bounds]
+ * receives bound_exit_pupil over n_bounds equal bands of half the film diagonal (:573-652: 1024^2 samples each).  focus_binary_search (:92) is not run: its
+ * result is discarded there.  Where the reference panics — "Coefficient must be positive" (focus distance too short), "Unable to trace ray ... for thick
+ * lens approximation", a negative t — the answer is RSPT_E_INVALID with that wording in rspt_last_error.  n_threads <= 0: min(16, host cores); the result
+ * does not depend on it. */
+int rspt_realistic_camera_setup(const float* lens_data, uint32_t n_elements, float aperture_diameter_mm, float focus_distance, float film_diagonal_mm,
+                                uint32_t n_bounds, rspt_lens_element* elements_out, float* bounds_out, int32_t n_threads);
+
+/* Stage-level hook (ABI 26).  Replaces: Camera::generate_ray_differential for n CameraSamples (samples: n x (p_film.x, p_film.y, time, p_lens.x, p_lens.y)) by
+ * the __device__ function the raygen kernel calls.  out: n x 22 floats = weight, o[3], d[3], t_max, time, rx_o[3], rx_d[3], ry_o[3], ry_d[3], has_diff
+ * (1 / 0: ray.differential is Some), in world space, differentials unscaled, as the reference function leaves its ray (a vignetted primary ray: the default
+ * ray, all zeros; the differentials are zeros wherever the weight is 0).  Served for RSPT_CAMERA_REALISTIC; the other kinds answer RSPT_E_UNSUPPORTED. */
+int rspt_camera_rays(const rspt_render_desc* desc, const float* samples, uint64_t n, float* out);
 
 /* The hash of the kernel / ABI sources this binary was built from (16 hex digits; csrc/Makefile SRC_HASH): rocprofv3 summaries under
  * profiles/ carry it, and a measurement quotes a profile only when the LIBRARY that is running reports the same hash. */

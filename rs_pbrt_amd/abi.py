@@ -4,7 +4,7 @@ Every struct here must stay byte-compatible with the header; tests/test_abi.py c
 sizes against the values the library reports."""
 import ctypes as C
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 OK, E_INVALID, E_NODEVICE, E_HIP, E_UNSUPPORTED, E_NOMEM, E_PEER = 0, -1, -2, -3, -4, -5, -6
 
@@ -20,7 +20,8 @@ INTEGRATOR_PATH, INTEGRATOR_AO, INTEGRATOR_DIRECT, INTEGRATOR_VOLPATH, INTEGRATO
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
 DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_UNIFORM, LIGHTS_POWER, LIGHTS_SPATIAL = 0, 1, 2
-CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT = 0, 1, 2      # ABI 25: rspt_render_desc.camera_kind (0 = what a zero-filled desc always meant)
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT, CAMERA_REALISTIC = 0, 1, 2, 3      # rspt_render_desc.camera_kind (0 = what a zero-filled desc always meant); 3: ABI 26
+MAX_LENS_ELEMENTS = 32
 TEX_CONSTANT, TEX_IMAGE, TEX_SCALE, TEX_MIX, TEX_CHECKERBOARD, TEX_DOTS, TEX_FBM, TEX_MARBLE, TEX_WINDY, TEX_WRINKLED = range(1, 11)
 MAP_UV, MAP_PLANAR, MAP_SPHERICAL, MAP_CYLINDRICAL, MAP_IDENTITY3D = 1, 2, 3, 4, 5
 WRAP_REPEAT, WRAP_BLACK, WRAP_CLAMP = 0, 1, 2
@@ -136,7 +137,14 @@ class RenderDesc(C.Structure):
                 ("strat_x", C.c_uint32), ("strat_y", C.c_uint32), ("strat_jitter", C.c_uint32), ("allow_slow_paths", C.c_uint32), ("maxmin_c_pixel", C.c_void_p),
                 ("sample_begin", C.c_uint64), ("sample_count", C.c_uint64),
                 ("camera_animated", C.c_uint32), ("camera_to_world_end", C.c_float * 16), ("camera_time", C.c_float * 2),
-                ("camera_kind", C.c_uint32)]      # ABI 25: in what was the tail padding, sizeof unchanged
+                ("camera_kind", C.c_uint32),      # ABI 25: in what was the tail padding
+                # ABI 26, CAMERA_REALISTIC only: rspt_lens_element[] (LENS_ELEMENT_DT), n x 4 floats of exit-pupil bounds, Film::diagonal in metres
+                ("lens_elements", C.c_void_p), ("n_lens_elements", C.c_uint32), ("exit_pupil_bounds", C.c_void_p), ("n_exit_pupil_bounds", C.c_uint32),
+                ("film_diagonal", C.c_float), ("lens_simple_weighting", C.c_uint32)]
+
+
+class LensElement(C.Structure):
+    _fields_ = [("curvature_radius", C.c_float), ("thickness", C.c_float), ("eta", C.c_float), ("aperture_radius", C.c_float)]
 
 
 class Ray(C.Structure):
@@ -179,6 +187,7 @@ TEXTURE_DT = np.dtype([("kind", "<u4"), ("mapping", "<u4"), ("map", "<f4", 8), (
 LIGHT_DT = np.dtype([("kind", "<u4"), ("prim", "<u4"), ("L", "<f4", 3), ("two_sided", "<u4"), ("p", "<f4", 24)])
 OBJECT_DT = np.dtype([("first_node", "<u8"), ("n_nodes", "<u8"), ("first_prim", "<u8"), ("n_prims", "<u8")])
 INSTANCE_DT = np.dtype([("object", "<u4"), ("to_world", "<f4", 16), ("from_world", "<f4", 16), ("animated", "<u4"), ("to_world_end", "<f4", 16), ("from_world_end", "<f4", 16), ("time", "<f4", 2)])
+LENS_ELEMENT_DT = np.dtype([("curvature_radius", "<f4"), ("thickness", "<f4"), ("eta", "<f4"), ("aperture_radius", "<f4")])
 RAY_DT = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("id", "<u4")])
 HIT_DT = np.dtype([("prim", "<u4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4")])
 
@@ -191,3 +200,4 @@ assert TEXTURE_DT.itemsize == C.sizeof(Texture) == 160
 assert RAY_DT.itemsize == C.sizeof(Ray) == 32
 assert HIT_DT.itemsize == C.sizeof(Hit) == 20
 assert LIGHT_DT.itemsize == C.sizeof(Light) == 120
+assert LENS_ELEMENT_DT.itemsize == C.sizeof(LensElement) == 16

@@ -2,6 +2,7 @@
 // (raygen / shade) or one pixel (film); wave64 throughout, no MFMA (pointer chasing + scalar
 // f32/f64 arithmetic, HBM/L2-latency bound).  Stage inventory:
 //   k_raygen        K1  Sampler::get_camera_sample + PerspectiveCamera::generate_ray_differential
+//   k_raygen_lens   K1  the same for RealisticCamera: the lens-system tracer (dev_lens.h), ray weights, dead samples
 //   k_trace<ANY>    K2/K3  BVHAccel::intersect / intersect_p + Triangle hit test, LDS-staged stack
 //   k_shade         K4+K6  PathIntegrator::li body between two intersections, incl. NEE resolve
 //   k_film          K8  FilmTile::add_sample / merge_film_tile
@@ -11,6 +12,7 @@
 #pragma once
 #include "dev_texture.h"
 #include "dev_sphere.h"
+#include "dev_lens.h"
 #include "pixel_sampler.h"
 
 namespace rspt {
@@ -95,6 +97,11 @@ struct PathBuf {
     uint32_t* orig;       // original slot of the path at position p (not read in the fresh launch: position = slot there)
     rspt_ray* o_ray_cont; float4* o_L_eta; float4* o_beta; float4* o_nee_c1; uint64_t* o_sobol_index; uint32_t* o_state; uint32_t* o_orig;
     float4* L_final;      // (L.rgb, -) by original slot, written once when the path ends
+    // ---- ABI 26: the realistic camera (k_raygen_lens); nullptr under every other camera ----
+    float* ray_weight;    // generate_ray_differential's weight by original slot: what the film stage multiplies a sample's radiance by (film.rs:94-147); a slot of
+                          // weight 0 is dead from the start: no ST_ALIVE, a camera ray that cannot hit, li never evaluated (integrator.rs:149)
+    float4* cam_diff;     // the camera ray's rx_o, rx_d, ry_o, ry_d (unscaled) by original slot, 3 x float4 each: what texture_slot would otherwise need four more
+                          // lens traces for (nullptr: scene without textures)
 };
 
 struct QueueCounts {  // one per wavefront iteration
@@ -192,6 +199,115 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_raygen(RenderDev rd, Batch bt, P
     if (pb.time) pb.time[i] = rd.shutter_open * (1.0f - p_lens.z) + rd.shutter_close * p_lens.z;   // lerp(sample.time, shutter_open, shutter_close)
     q_active[i] = i;
     q_closest[i] = i;
+}
+
+// ---- K1 for RSPT_CAMERA_REALISTIC (ABI 26) ------------------------------------------------------
+// k_raygen's sampler code with RealisticCamera::generate_ray_differential (dev_lens.h) behind it; k_raygen itself keeps its text and its registers.  The lens
+// dimensions (3, 4) are always drawn.  The interface table (wave-uniform reads) and the exit-pupil bounds (indexed per lane by the film radius) are copied into
+// LDS once per block.  A sample of weight 0 — vignetted, or both signs of a shift vignetted — is dead from the start: its slot gets no ST_ALIVE, so the first
+// shade launch ends it with L = 0 before it could look at a hit record (shade_path) and k_ao_spawn spawns nothing for it; it stays in the queues with a camera
+// ray that cannot hit (t_max < 0).  Keeping it out of the closest-hit queue would cost a ballot and an atomic per wave and break position = slot, which the
+// first MOVE launch and the film stage rely on; a ray that misses the root box costs the traversal one box test.
+#define RSPT_MAX_EXIT_PUPIL_BOUNDS 64
+RDEV void lens_tables_to_lds(const LensSystem& lens, rspt_lens_element* s_el, float* s_bounds, LensSystem* L) {
+    for (uint32_t t = threadIdx.x; t < lens.n_elements; t += blockDim.x) s_el[t] = lens.elements[t];
+    for (uint32_t t = threadIdx.x; t < 4u * lens.n_bounds; t += blockDim.x) s_bounds[t] = lens.bounds[t];
+    __syncthreads();
+    *L = lens;
+    L->elements = s_el; L->bounds = s_bounds;
+}
+RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_raygen_lens(RenderDev rd, LensSystem lens, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
+                                                     uint32_t* __restrict__ q_active, uint32_t* __restrict__ q_closest, QueueCounts* cnt) {
+    uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) { cnt->active = bt.n; cnt->closest = bt.n; cnt->any = 0; }
+    __shared__ uint64_t s_vdc[2][52];
+    __shared__ uint32_t s_gen[5][52];
+    __shared__ rspt_lens_element s_el[RSPT_MAX_LENS_ELEMENTS];
+    __shared__ float s_bounds[4 * RSPT_MAX_EXIT_PUPIL_BOUNDS];
+    const bool sobol = rd.sampler_kind != RSPT_SAMPLER_HALTON;
+    const uint32_t m = (uint32_t)rd.log2_res;
+    if (sobol) {
+        for (uint32_t t = threadIdx.x; t < 5u * 52u; t += 256u) s_gen[t / 52u][t % 52u] = rd.sobol32[t];
+        if (m > 0u && threadIdx.x < 104u) s_vdc[threadIdx.x / 52u][threadIdx.x % 52u] = (threadIdx.x < 52u ? rd.vdc : rd.vdc_inv)[(m - 1u) * 52u + threadIdx.x % 52u];
+    }
+    LensSystem L;
+    lens_tables_to_lds(lens, s_el, s_bounds, &L);   // (its barrier covers the Sobol' tables too)
+    if (i >= bt.n) return;
+    uint32_t k = bt.pix0 + i / bt.ns, s = bt.s0 + i % bt.ns;
+    uint32_t pk = pix_list[k];
+    int32_t px = (int32_t)(int16_t)(pk & 0xffffu), py = (int32_t)(int16_t)(pk >> 16);
+    uint64_t index;
+    float fx, fy;
+    f3 p_lens{0.0f, 0.0f, 0.0f};   // (lens x, lens y, time)
+    if (!sobol) {
+        index = halton_index(rd, px, py, (uint64_t)s);
+        fy = halton_dim(rd, index, 1); fx = halton_dim(rd, index, 0);
+        if (rd.cam_anim || pb.time) p_lens.z = halton_dim(rd, index, 2);
+        p_lens.x = halton_dim(rd, index, 3); p_lens.y = halton_dim(rd, index, 4);
+    } else {
+        index = 0;
+        if (m > 0u) {
+            index = (uint64_t)s << (m << 1);
+            uint64_t delta = 0;
+            for (uint64_t f = (uint64_t)s; f != 0; f &= f - 1) delta ^= s_vdc[0][__builtin_ctzll(f)];
+            uint64_t b = ((uint64_t)((uint32_t)(px - rd.sample_bounds[0]) << m) | (uint64_t)(int64_t)(py - rd.sample_bounds[1])) ^ delta;
+            for (; b != 0; b &= b - 1) index ^= s_vdc[1][__builtin_ctzll(b)];
+        }
+        auto dim = [&](uint32_t dnum) {
+            uint32_t v = 0;
+            for (uint64_t a = index; a != 0; a &= a - 1) v ^= s_gen[dnum][__builtin_ctzll(a)];
+            return fminf((float)v * 0x1.0p-32f, RSPT_ONE_MINUS_EPS);
+        };
+        auto pixel_dim = [&](uint32_t dnum, int32_t pix) {
+            const float sv = dim(dnum) * (float)rd.resolution + (float)rd.sample_bounds[dnum];
+            return clampf(sv - (float)pix, 0.0f, RSPT_ONE_MINUS_EPS);
+        };
+        fy = pixel_dim(1, py); fx = pixel_dim(0, px);
+        if (rd.cam_anim || pb.time) p_lens.z = dim(2);
+        p_lens.x = dim(3); p_lens.y = dim(4);
+    }
+    f2 p_film{(float)px + fx, (float)py + fy};
+    LensRayOut ray;
+    const float wt = lens_ray_differential(rd, L, p_film.x, p_film.y, p_lens.z, p_lens.x, p_lens.y, &ray);
+    const bool alive = wt > 0.0f;   // integrator.rs:149
+    rspt_ray r;
+    if (alive) { r.o[0] = ray.o.x; r.o[1] = ray.o.y; r.o[2] = ray.o.z; r.d[0] = ray.d.x; r.d[1] = ray.d.y; r.d[2] = ray.d.z; r.t_max = ray.t_max; }
+    else { r.o[0] = r.o[1] = r.o[2] = 0.0f; r.d[0] = r.d[1] = r.d[2] = 0.57735026f; r.t_max = -1.0f; }
+    r.id = i;
+    pb.ray_cont[i] = r;
+    if (!pb.fresh) {
+        pb.L_eta[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        pb.beta[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    }
+    pb.sobol_index[i] = index;
+    pb.state[i] = alive ? (5u | ST_ALIVE) : 5u;
+    pb.p_film[i] = make_float2(p_film.x, p_film.y);
+    pb.ray_weight[i] = wt;
+    if (pb.cam_diff) {
+        pb.cam_diff[3 * (size_t)i] = make_float4(ray.rx_o.x, ray.rx_o.y, ray.rx_o.z, ray.rx_d.x);
+        pb.cam_diff[3 * (size_t)i + 1] = make_float4(ray.rx_d.y, ray.rx_d.z, ray.ry_o.x, ray.ry_o.y);
+        pb.cam_diff[3 * (size_t)i + 2] = make_float4(ray.ry_o.z, ray.ry_d.x, ray.ry_d.y, ray.ry_d.z);
+    }
+    if (pb.time) pb.time[i] = rd.shutter_open * (1.0f - p_lens.z) + rd.shutter_close * p_lens.z;
+    q_active[i] = i;
+    q_closest[i] = i;
+}
+// stage hook rspt_camera_rays: lens_ray_differential, the function k_raygen_lens calls, over given CameraSamples (5 floats in, 22 floats out: include/rspt.h)
+RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_camera_rays(RenderDev rd, LensSystem lens, const float* __restrict__ smp, uint64_t n, float* __restrict__ out) {
+    __shared__ rspt_lens_element s_el[RSPT_MAX_LENS_ELEMENTS];
+    __shared__ float s_bounds[4 * RSPT_MAX_EXIT_PUPIL_BOUNDS];
+    LensSystem L;
+    lens_tables_to_lds(lens, s_el, s_bounds, &L);
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float* q = smp + 5 * i;
+    LensRayOut ray;
+    const float wt = lens_ray_differential(rd, L, q[0], q[1], q[2], q[3], q[4], &ray);
+    float* o = out + 22 * i;
+    o[0] = wt; o[1] = ray.o.x; o[2] = ray.o.y; o[3] = ray.o.z; o[4] = ray.d.x; o[5] = ray.d.y; o[6] = ray.d.z; o[7] = ray.t_max; o[8] = ray.time;
+    const f3 v[4] = {ray.rx_o, ray.rx_d, ray.ry_o, ray.ry_d};
+    for (int j = 0; j < 4; j++) { o[9 + 3 * j] = v[j].x; o[10 + 3 * j] = v[j].y; o[11 + 3 * j] = v[j].z; }
+    o[21] = wt != 0.0f ? 1.0f : 0.0f;   // ray.differential is Some
 }
 
 // ---- K2 / K3 --------------------------------------------------------------------------------
@@ -961,6 +1077,13 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
             if (rd.cam_anim) p_lens.z = hal ? halton_dim(rd, index, 2) : sobol_dim(rd, index, 2);
         }
         f3 rx_o, rx_d, ry_o, ry_d;
+        if (rd.camera_kind == RSPT_CAMERA_REALISTIC) {   // k_raygen_lens stored the four vectors (recomputing them is four lens traces); scale_differentials here
+            const float4 c0 = pb.cam_diff[3 * (size_t)smp], c1 = pb.cam_diff[3 * (size_t)smp + 1], c2 = pb.cam_diff[3 * (size_t)smp + 2];
+            const f3 ro{r0.x, r0.y, r0.z}, rdir{r0.w, r1.x, r1.y};
+            const float sc_ = 1.0f / sqrtf((float)rd.spp);
+            rx_o = ro + (f3{c0.x, c0.y, c0.z} - ro) * sc_; ry_o = ro + (f3{c1.z, c1.w, c2.x} - ro) * sc_;
+            rx_d = rdir + (f3{c0.w, c1.x, c1.y} - rdir) * sc_; ry_d = rdir + (f3{c2.y, c2.z, c2.w} - rdir) * sc_;
+        } else
         camera_differentials(rd, f2{pf.x, pf.y}, p_lens, f3{r0.x, r0.y, r0.z}, f3{r0.w, r1.x, r1.y}, &rx_o, &rx_d, &ry_o, &ry_d);
         compute_differentials(h, rx_o, rx_d, ry_o, ry_d, &s);
     }
@@ -1247,8 +1370,9 @@ __device__ __forceinline__ void ao_spawn(SceneDev sc, RenderDev rd, Batch bt, Pa
     if (i >= bt.n) return;
     const float4 hc = pb.hit_cont[i];
     const uint32_t prim = __float_as_uint(hc.x);
-    pb.state[i] = prim == RSPT_MISS ? 0u : 1u;
-    if (prim == RSPT_MISS) return;
+    const bool dead = pb.ray_weight && !(pb.ray_weight[i] > 0.0f);   // the realistic camera's weight-0 samples: li is never called (integrator.rs:149)
+    pb.state[i] = (prim == RSPT_MISS || dead) ? 0u : 1u;
+    if (prim == RSPT_MISS || dead) return;
     const float4* rp = reinterpret_cast<const float4*>(pb.ray_cont + i);
     const float4 r0 = rp[0], r1 = rp[1];
     const f3 ray_d{r0.w, r1.x, r1.y};
@@ -1386,6 +1510,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_film(RenderDev rd, Batch bt, Pat
             o[0] = l.r; o[1] = l.g; o[2] = l.b;
         }
         if (lum(l) > rd.max_sample_luminance) l = l * mkrgb(rd.max_sample_luminance / lum(l));
+        const float rw = pb.ray_weight ? pb.ray_weight[(size_t)k * bt.ns + j] : 1.0f;   // the camera's ray weight: 1 except under the realistic camera
         float2 pf = s_pf[threadIdx.x * RSPT_FILM_ROW + jc];
         float dx = pf.x - 0.5f, dy = pf.y - 0.5f;
         int32_t x0 = max(f2i_sat(ceilf(dx - rx)), bx0), y0 = max(f2i_sat(ceilf(dy - ry)), by0);
@@ -1397,7 +1522,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_film(RenderDev rd, Batch bt, Pat
                 float fx = fabsf(((float)x - dx) * inv_rx * 16.0f);
                 int32_t ifx = (int32_t)fminf(floorf(fx), 15.0f);
                 float w = rd.filter_table[ify * 16 + ifx];
-                rgb c = l * mkrgb(1.0f) * mkrgb(w);  // l * sample_weight * filter_weight
+                rgb c = l * mkrgb(rw) * mkrgb(w);  // l * sample_weight * filter_weight
                 if (x == px && y == py) {
                     acc.x += c.r; acc.y += c.g; acc.z += c.b; acc.w += w;
                 } else {
@@ -1482,6 +1607,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_film_gather(RenderDev rd, Batch 
                     o[0] = l.r; o[1] = l.g; o[2] = l.b;
                 }
                 if (lum(l) > rd.max_sample_luminance) l = l * mkrgb(rd.max_sample_luminance / lum(l));
+                if (pb.ray_weight) l = l * mkrgb(pb.ray_weight[slot]);   // sample_weight, applied here so that the sum below stays (l * sample_weight) * filter_weight
                 const float dx = pf.x - 0.5f, dy = pf.y - 0.5f;
                 // the footprint (film.rs:104-116); a FilmTile's own pixel bounds never cut it (they are the tile's sample bounds grown by the radius), the crop window does
                 const int32_t x0 = max(f2i_sat(ceilf(dx - rx)), cp[0]) - bx, y0 = max(f2i_sat(ceilf(dy - ry)), cp[1]) - by;
@@ -1511,7 +1637,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_film_gather(RenderDev rd, Batch 
                     const float fx = fabsf(((float)x - a.w) * inv_rx * 16.0f);
                     const int32_t ifx = (int32_t)fminf(floorf(fx), 15.0f);
                     const float w = s_tab[ify * 16 + ifx];
-                    const rgb c = rgb{a.x, a.y, a.z} * mkrgb(1.0f) * mkrgb(w);  // l * sample_weight * filter_weight
+                    const rgb c = rgb{a.x, a.y, a.z} * mkrgb(1.0f) * mkrgb(w);  // l * sample_weight * filter_weight (the realistic camera's weight is in a already)
                     acc.x += c.r; acc.y += c.g; acc.z += c.b; acc.w += w;
                 }
             }

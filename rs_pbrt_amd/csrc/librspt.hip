@@ -14,7 +14,9 @@
 #include <functional>
 #include <limits>
 #include <map>
+#include <atomic>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/rspt.h"
@@ -89,6 +91,12 @@ struct Ctx {
     size_t hit_inst_cap = 0;
     float* path_time = nullptr;        // per path slot: Ray.time (scenes with moving instances)
     size_t time_cap = 0;
+    float* ray_weight = nullptr;       // per path slot: the realistic camera's ray weight (kernels.h PathBuf::ray_weight)
+    size_t ray_weight_cap = 0;
+    float4* cam_diff = nullptr;        // per path slot: the realistic camera's differentials for the texture stage (PathBuf::cam_diff), 3 per slot
+    size_t cam_diff_cap = 0;
+    rspt_lens_element* lens_elements = nullptr;   // the realistic camera's two tables, uploaded per render (render_run.h upload_lens)
+    float* lens_bounds = nullptr;
     unsigned long long* totals = nullptr;  // [0] nodes [1] tris [2] bsdf hits [3] rays closest [4] rays any [5] nan samples
     // sampler tables + filter table
     uint32_t* sobol32 = nullptr;
@@ -325,6 +333,9 @@ void free_paths() {
         if (p) (void)hipFree(p);
     if (g.path_time) (void)hipFree(g.path_time);   // sized with the path buffers (RenderRun::prepare), freed with them
     g.path_time = nullptr; g.time_cap = 0;
+    if (g.ray_weight) (void)hipFree(g.ray_weight);   // the realistic camera's per-slot arrays: sized and freed the same way
+    if (g.cam_diff) (void)hipFree(g.cam_diff);
+    g.ray_weight = nullptr; g.ray_weight_cap = 0; g.cam_diff = nullptr; g.cam_diff_cap = 0;
     g.pb = PathBuf{};
     g.tex_rows = 0;
     for (auto& a : g.q) a[0] = a[1] = a[2] = nullptr;
@@ -696,7 +707,7 @@ void rspt_shutdown(void) {
     (void)hipSetDevice(g.device);
     (void)hipStreamSynchronize(g.stream);
     free_paths();
-    void* ptrs[] = {g.dl.le_kind, g.dl.w_r, g.dl.w_t, g.dl.l_all, g.dl.ld_acc, g.dl.dim, g.dl.kidx, g.dl.nflags, g.dl.error, g.dl_queue, g.bin_keys, g.q_sorted, g.bin_info, g.hit_inst, g.cnt, g.ovf, g.spill, g.totals, g.sobol32, g.vdc, g.vdc_inv, g.filter_table, g.film_own, g.film_splat, g.film_out, g.pix_list, g.pix_index, g.primes, g.prime_sums, g.halton_perms, g.cam_anim};
+    void* ptrs[] = {g.dl.le_kind, g.dl.w_r, g.dl.w_t, g.dl.l_all, g.dl.ld_acc, g.dl.dim, g.dl.kidx, g.dl.nflags, g.dl.error, g.dl_queue, g.bin_keys, g.q_sorted, g.bin_info, g.hit_inst, g.cnt, g.ovf, g.spill, g.totals, g.sobol32, g.vdc, g.vdc_inv, g.filter_table, g.film_own, g.film_splat, g.film_out, g.pix_list, g.pix_index, g.primes, g.prime_sums, g.halton_perms, g.cam_anim, g.lens_elements, g.lens_bounds};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : g.events) (void)hipEventDestroy(e);
@@ -1572,6 +1583,109 @@ int rspt_camera_decompose(const float start_m[16], float start_time, const float
     }
     return RSPT_OK;
 }
+// RealisticCamera::new (realistic.rs:50-144) up to the state it builds, over the host side of dev_lens.h.  focus_binary_search (:92) is left out: the
+// reference discards its result (`_fb`) and it changes no state.
+int rspt_realistic_camera_setup(const float* lens_data, uint32_t n_elements, float aperture_diameter_mm, float focus_distance, float film_diagonal_mm,
+                                uint32_t n_bounds, rspt_lens_element* elements_out, float* bounds_out, int32_t n_threads) {
+    if (!lens_data || !elements_out || !bounds_out) return fail(RSPT_E_INVALID, "null argument");
+    if (n_elements == 0 || n_elements > RSPT_MAX_LENS_ELEMENTS) return fail(RSPT_E_INVALID, "n_elements must be in [1, %d]", RSPT_MAX_LENS_ELEMENTS);
+    if (n_bounds == 0 || n_bounds > (1u << 16)) return fail(RSPT_E_INVALID, "n_bounds must be in [1, 65536]");
+    std::vector<rspt_lens_element> el(n_elements);
+    for (uint32_t i = 0; i < n_elements; i++) {   // :61-80: mm -> m; a stop takes the given aperture unless that exceeds the file's ("Clamping it.")
+        const float* q = lens_data + 4 * (size_t)i;
+        float diameter = q[3];
+        if (q[0] == 0.0f && !(aperture_diameter_mm > q[3])) diameter = aperture_diameter_mm;
+        el[i] = rspt_lens_element{q[0] * 0.001f, q[1] * 0.001f, q[2], diameter * 0.001f / 2.0f};
+    }
+    const float diagonal = film_diagonal_mm * 0.001f;   // Film::new (film.rs:214)
+    uint32_t t_neg = 0;
+    // focus_thick_lens (:483-499) over compute_thick_lens_approximation (:444-482) and compute_cardinal_points (:431-443)
+    float pz[2], fz[2];
+    {
+        const float x = 0.001f * diagonal;
+        auto cardinal = [&](const LensRay& r_in, const LensRay& r_out, int idx) {
+            const float tf = -r_out.o.x / r_out.d.x;
+            fz[idx] = -(r_out.o.z + r_out.d.z * tf);
+            const float tp = (r_in.o.x - r_out.o.x) / r_out.d.x;
+            pz[idx] = -(r_out.o.z + r_out.d.z * tp);
+        };
+        LensRay r_scene{lv3{x, 0.0f, lens_front_z(el.data(), n_elements) + 1.0f}, lv3{0.0f, 0.0f, -1.0f}, RSPT_INF}, r_film{};
+        if (!lens_trace_from_scene(el.data(), n_elements, r_scene, &r_film, &t_neg))
+            return fail(RSPT_E_INVALID, "Unable to trace ray from scene to film for thick lens approximation. Is aperture stop extremely small?");
+        cardinal(r_scene, r_film, 0);
+        r_film.o = lv3{x, 0.0f, el.back().thickness - 1.0f};
+        r_film.d = lv3{0.0f, 0.0f, 1.0f};
+        if (!lens_trace_from_film(el.data(), n_elements, r_film, &r_scene, &t_neg))
+            return fail(RSPT_E_INVALID, "Unable to trace ray from film to scene for thick lens approximation. Is aperture stop extremely small?");
+        cardinal(r_film, r_scene, 1);
+    }
+    const float f = fz[0] - pz[0], z = -focus_distance;
+    const float c = (pz[1] - z - pz[0]) * (pz[1] - z - 4.0f * f - pz[0]);
+    if (!(c > 0.0f))
+        return fail(RSPT_E_INVALID, "Coefficient must be positive. It looks focus_distance: %g is too short for a given lenses configuration", (double)focus_distance);
+    const float delta = 0.5f * (pz[1] - z + pz[0] - std::sqrt(c));
+    el.back().thickness = el.back().thickness + delta;
+    // bound_exit_pupil over the bands of half the diagonal (:100-139); a band's box is a min / max over the points that pass, so the split over threads cannot show
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const unsigned nt = std::max(1u, std::min({16u, n_threads > 0 ? (unsigned)n_threads : hw, n_bounds}));
+    std::atomic<uint32_t> next{0}, neg{0};
+    auto worker = [&]() {
+        uint32_t tn = 0;
+        for (;;) {
+            const uint32_t i = next.fetch_add(1);
+            if (i >= n_bounds) break;
+            const float r0 = (float)i / (float)n_bounds * diagonal / 2.0f, r1 = (float)(i + 1u) / (float)n_bounds * diagonal / 2.0f;
+            lens_bound_exit_pupil(el.data(), n_elements, r0, r1, bounds_out + 4 * (size_t)i, &tn);
+        }
+        neg += tn;
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(worker);
+    worker();
+    for (auto& t : th) t.join();
+    if (t_neg + neg.load()) return fail(RSPT_E_INVALID, "assertion failed: t >= 0.0 (a lens interface was met behind the ray's origin, %u times)", t_neg + neg.load());
+    memcpy(elements_out, el.data(), n_elements * sizeof(rspt_lens_element));
+    return RSPT_OK;
+}
+
+int rspt_camera_rays(const rspt_render_desc* d, const float* samples, uint64_t n, float* out) {
+    if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
+    if (!d || (n && (!samples || !out))) return fail(RSPT_E_INVALID, "null argument");
+    if (int rc = validate_camera(d)) return rc;
+    if (d->camera_kind != RSPT_CAMERA_REALISTIC) return fail(RSPT_E_UNSUPPORTED, "rspt_camera_rays serves camera_kind 3 (realistic) only");
+    if (n == 0) return RSPT_OK;
+    if (n > (1ull << 28)) return fail(RSPT_E_INVALID, "more than 2^28 camera samples in one call");
+    HIP_TRY(hipSetDevice(g.device));
+    int rc;
+    RenderDev rd{};
+    memcpy(rd.camera_to_world, d->camera_to_world, sizeof rd.camera_to_world);
+    rd.camera_kind = d->camera_kind; rd.full_res[0] = d->full_res[0]; rd.full_res[1] = d->full_res[1];
+    rd.shutter_open = d->shutter_open; rd.shutter_close = d->shutter_close;
+    rd.spp = d->spp;
+    if (d->camera_animated) {
+        CamAnim ca;
+        if (camanim::camera_keys(d->camera_to_world, d->camera_time[0], d->camera_to_world_end, d->camera_time[1], &ca)) {
+            if (!g.cam_anim && (rc = dev_alloc(&g.cam_anim, 1))) return rc;
+            HIP_TRY(hipMemcpy(g.cam_anim, &ca, sizeof ca, hipMemcpyHostToDevice));
+            rd.cam_anim = g.cam_anim;
+        }
+    }
+    LensSystem lens;
+    if ((rc = upload_lens(d, &lens))) return rc;
+    DevTemps temps;
+    float *smp_dev = nullptr, *out_dev = nullptr;
+    if ((rc = dev_alloc(&smp_dev, 5 * n))) return rc;
+    temps.p.push_back(smp_dev);
+    if ((rc = dev_alloc(&out_dev, 22 * n))) return rc;
+    temps.p.push_back(out_dev);
+    HIP_TRY(hipMemcpyAsync(smp_dev, samples, 5 * n * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, rd, lens, smp_dev, n, out_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, out_dev, 22 * n * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RSPT_OK;
+}
+
 int rspt_motion_bounds(const float start_m[16], float start_time, const float end_m[16], float end_time, const float box_min[3], const float box_max[3],
                        float out_min[3], float out_max[3], int32_t* flags_out) {
     if (!start_m || !end_m || !box_min || !box_max || !out_min || !out_max) return fail(RSPT_E_INVALID, "null argument");

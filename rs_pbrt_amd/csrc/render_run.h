@@ -11,12 +11,12 @@ struct RenderRun {
     const rspt_render_desc* d; rspt_render_desc wd;   // the caller's desc, or `wd`: whitted's, rewritten for directlighting's machinery
     RenderRun(rspt_scene_s* s_, const rspt_render_desc* d_) : s(s_), d(d_) {}  RenderRun(const RenderRun&) = delete;   // (d may point at wd)
     // validate(): integrator, sampler, sample range, shard
-    bool whitted = false, multi_lobes = true, halton = false, sobol = false, pixel_sampler = false, direct = false, volpath = false;
+    bool whitted = false, multi_lobes = true, halton = false, sobol = false, pixel_sampler = false, direct = false, volpath = false, realistic = false;
     const char* dl_name = "directlighting";
     uint64_t smp_begin = 0, smp_end = 0;
     const int32_t* sb = nullptr; const int32_t* cp = nullptr; uint32_t shard_count = 1, chunk = 1;
     // constants(): render constants, sampler tables, light distribution (ld_lazy: on-demand voxels, a mark / build round in front of every shade launch)
-    RenderDev rd{}; uint32_t vol_dim_limit = 1024u;
+    RenderDev rd{}; uint32_t vol_dim_limit = 1024u; LensSystem lens{};   // lens: RSPT_CAMERA_REALISTIC only
     LightDistDev ld; const LightDist* ld_lazy = nullptr;
     // shard_pixels(): tiles of the whole frame, this shard's in Morton order, their pixels (the list outlives its asynchronous upload)
     int32_t ts = 0, ntx = 0; size_t n_blocks = 0, n_pix = 0;
@@ -60,12 +60,48 @@ struct RenderRun {
     TraceCall any_call(const PathBuf& P, const uint32_t* queue, const uint32_t* n, uint32_t* cursor, bool count) const { return trace_call(true, P, queue, n, cursor, count); }
 };
 
+// The camera part of a render desc (rspt_render and its siblings, rspt_camera_rays): every refusal names camera_kind
+int validate_camera(const rspt_render_desc* d) {
+    if (d->camera_kind > RSPT_CAMERA_REALISTIC) return fail(RSPT_E_INVALID, "camera_kind %u (0 perspective, 1 orthographic, 2 environment, 3 realistic)", d->camera_kind);
+    if (d->camera_kind == RSPT_CAMERA_ENVIRONMENT && (d->full_res[0] <= 0 || d->full_res[1] <= 0)) return fail(RSPT_E_INVALID, "camera_kind environment: full_res must be positive");
+    if (d->camera_kind == RSPT_CAMERA_REALISTIC) {
+        if (!d->lens_elements || d->n_lens_elements == 0) return fail(RSPT_E_INVALID, "camera_kind realistic: the lens element table is null or empty (rspt_realistic_camera_setup builds it)");
+        if (d->n_lens_elements > RSPT_MAX_LENS_ELEMENTS) return fail(RSPT_E_INVALID, "camera_kind realistic: %u lens elements, at most %d are served", d->n_lens_elements, RSPT_MAX_LENS_ELEMENTS);
+        if (!d->exit_pupil_bounds || d->n_exit_pupil_bounds == 0) return fail(RSPT_E_INVALID, "camera_kind realistic: the exit pupil bounds table is null or empty (rspt_realistic_camera_setup builds it)");
+        if (d->n_exit_pupil_bounds > RSPT_MAX_EXIT_PUPIL_BOUNDS) return fail(RSPT_E_INVALID, "camera_kind realistic: %u exit pupil bounds, at most %d are served", d->n_exit_pupil_bounds, RSPT_MAX_EXIT_PUPIL_BOUNDS);
+        if (d->full_res[0] <= 0 || d->full_res[1] <= 0) return fail(RSPT_E_INVALID, "camera_kind realistic: full_res must be positive");
+        if (!(d->film_diagonal > 0.0f)) return fail(RSPT_E_INVALID, "camera_kind realistic: film_diagonal must be positive");
+    }
+    return RSPT_OK;
+}
+// the lens tables of a realistic camera in device memory (once per render / hook call) and what the tracer reads besides them
+int upload_lens(const rspt_render_desc* d, LensSystem* L) {
+    int rc;
+    if (!g.lens_elements && ((rc = dev_alloc(&g.lens_elements, RSPT_MAX_LENS_ELEMENTS)) || (rc = dev_alloc(&g.lens_bounds, 4 * RSPT_MAX_EXIT_PUPIL_BOUNDS)))) return rc;
+    HIP_TRY(hipMemcpyAsync(g.lens_elements, d->lens_elements, d->n_lens_elements * sizeof(rspt_lens_element), hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(g.lens_bounds, d->exit_pupil_bounds, d->n_exit_pupil_bounds * 4 * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    *L = LensSystem{g.lens_elements, g.lens_bounds, d->n_lens_elements, d->n_exit_pupil_bounds, d->film_diagonal, (float)d->full_res[0], (float)d->full_res[1],
+                    d->shutter_open, d->shutter_close, d->lens_simple_weighting ? 1u : 0u};
+    return RSPT_OK;
+}
 // Argument validation of a render: fills the integrator / sampler flags and the sample range from the desc, touches no device state
 int RenderRun::validate() {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
-    if (d->camera_kind > RSPT_CAMERA_ENVIRONMENT) return fail(RSPT_E_INVALID, "camera_kind %u (0 perspective, 1 orthographic, 2 environment)", d->camera_kind);
-    if (d->camera_kind == RSPT_CAMERA_ENVIRONMENT && (d->full_res[0] <= 0 || d->full_res[1] <= 0)) return fail(RSPT_E_INVALID, "camera_kind environment: full_res must be positive");
+    if (int rc = validate_camera(d)) return rc;
+    // ABI 26: the realistic camera is served where k_raygen_lens and the per-sample ray weight are: path and ao in the wavefront form (Sobol' / Halton).  The
+    // schedules of volpath, directlighting and whitted consume k_raygen's output in their own ways and the pixel samplers' per-tile walk makes its own camera
+    // rays (tile_serial.h): refused, so the caller keeps its CPU loop.
+    realistic = d->camera_kind == RSPT_CAMERA_REALISTIC;
+    if (realistic) {
+        static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
+        if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+            return fail(RSPT_E_UNSUPPORTED, "the realistic camera under the %s integrator: it is served by path and ao only (their schedules carry the ray weight)", d->integrator < 5 ? names[d->integrator] : "?");
+        if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+            return fail(RSPT_E_UNSUPPORTED, "the realistic camera under the %s sampler: it is served with the sobol and halton samplers only (a pixel sampler's tile walk makes its own camera rays)",
+                        d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                        d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+    }
     // Analytic spheres are served as surfaces (hit, shaded, textured, blocking light) by the path and AO integrators in their wavefront form
     // (Sobol' / Halton).  Everything else that holds a sphere is refused, so the caller keeps its CPU loop: sphere area lights (their
     // sample_with_ref_point / pdf_with_ref_point and power are not on the device), the directlighting / whitted / volpath forms and the pixel
@@ -180,6 +216,7 @@ int RenderRun::constants() {
         }
     }
     rd.shutter_open = d->shutter_open; rd.shutter_close = d->shutter_close;
+    if (realistic && (rc = upload_lens(d, &lens))) return rc;
     memcpy(rd.sample_bounds, sb, sizeof rd.sample_bounds);
     memcpy(rd.crop_px, cp, sizeof rd.crop_px);
     rd.resolution = round_up_pow2_32(std::max(sb[2] - sb[0], sb[3] - sb[1]));  // sobol.rs:46-47
@@ -448,6 +485,10 @@ int RenderRun::prepare() {
     s->dev.ray_time = g.pb.time;
     s->dev.time_div = 1u;
     g.pb.fresh = 0u;
+    // the realistic camera: a ray weight per sample, and the camera ray's differentials where a texture stage will want them
+    if (realistic && ((rc = ensure_array(&g.ray_weight, &g.ray_weight_cap, g.cap)) || (s->has_textures && (rc = ensure_array(&g.cam_diff, &g.cam_diff_cap, 3 * g.cap))))) return rc;
+    g.pb.ray_weight = realistic ? g.ray_weight : nullptr;
+    g.pb.cam_diff = (realistic && s->has_textures) ? g.cam_diff : nullptr;
     g.pb.hit_inst = s->has_instances ? g.hit_inst : nullptr;
     g.vol.hit_inst_tr = (volpath && s->has_instances) ? g.hit_inst + g.cap : nullptr;
     if ((rc = ensure_array(&g.cnt, &g.n_cnt, max_iters + 10)) || (rc = ensure_array(&g.ovf, &g.ovf_cap, trace_can_overflow(s) ? 3 * g.cap : 1024)) || (rc = ensure_spill(pw_spill_threads())) ||

@@ -469,6 +469,8 @@ int RenderRun::run() {
             // the path integrator's first shade launch knows what k_raygen would have written into L_eta / beta (PathBuf::fresh); RSPT_FRESH=0: written and read as before
             const bool fresh_ok = !volpath && !direct && !ao && env_size("RSPT_FRESH", 1) != 0;
             g.pb.fresh = fresh_ok ? 1u : 0u;
+            if (realistic) hipLaunchKernelGGL(k_raygen_lens, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, rd, lens, bt, g.pb, g.pix_list, g.q[0][0], g.q[0][1], g.cnt);   // (path and ao only: validate)
+            else
             hipLaunchKernelGGL(k_raygen, dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, rd, bt, g.pb, g.pix_list, g.q[0][0], g.q[0][1], g.cnt);   // (MOVE or not: iteration 0 lives in set 0 = pb's own arrays, by slot)
             uint32_t it = 0;
             queue_hint = 0xffffffffu;

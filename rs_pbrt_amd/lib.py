@@ -16,7 +16,8 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
            "rspt_render_device", "rspt_render_samples", "rspt_trace", "rspt_trace_device", "rspt_dev_alloc", "rspt_dev_free",
            "rspt_dev_upload", "rspt_dev_download", "rspt_last_error", "rspt_last_counters", "rspt_bvh_build", "rspt_bvh_last_error",
            "rspt_bvh_build_gpu", "rspt_bvh_build_bounds", "rspt_comm_unique_id", "rspt_comm_init", "rspt_comm_destroy", "rspt_light_distribution", "rspt_libm",
-           "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library")
+           "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library", "rspt_realistic_camera_setup",
+           "rspt_camera_rays")
 
 
 def tree_source_hash():
@@ -83,6 +84,8 @@ def lib():
         L.rspt_material_lobes.argtypes = [vp, u32, u32, vp, vp]
         L.rspt_camera_decompose.argtypes = [vp, C.c_float, vp, C.c_float, vp, vp]
         L.rspt_motion_bounds.argtypes = [vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, vp]
+        L.rspt_realistic_camera_setup.argtypes = [vp, u32, C.c_float, C.c_float, C.c_float, u32, vp, vp, i32]
+        L.rspt_camera_rays.argtypes = [vp, vp, u64, vp]
         L.rspt_source_hash.restype = C.c_char_p
         L.rspt_comm_library.restype = C.c_char_p
         L.rspt_comm_unique_id.argtypes = [vp]
@@ -108,6 +111,26 @@ def camera_decompose(rd):
     if not animated.value:
         return None
     return trs[:6].reshape(2, 3).copy(), trs[6:14].reshape(2, 4).copy(), trs[14:].reshape(2, 4, 4).copy()
+
+
+def realistic_camera_setup(lens_data, aperture_diameter, focus_distance, film_diagonal, n_bounds=64, threads=0):
+    """rspt_realistic_camera_setup (host only): what RealisticCamera::new (realistic.rs:50-144) builds from a lens file's numbers (n x 4, millimetres), the
+    aperture diameter and the film diagonal in mm and the focus distance -> (elements LENS_ELEMENT_DT[n] in metres, focused; bounds (n_bounds, 4) f32)"""
+    data = np.ascontiguousarray(lens_data, np.float32).reshape(-1, 4)
+    elements = np.zeros(len(data), abi.LENS_ELEMENT_DT)
+    bounds = np.zeros((int(n_bounds), 4), np.float32)
+    _check(lib().rspt_realistic_camera_setup(data.ctypes.data, len(data), float(aperture_diameter), float(focus_distance), float(film_diagonal), int(n_bounds),
+                                             elements.ctypes.data, bounds.ctypes.data, int(threads)))
+    return elements, bounds
+
+
+def camera_rays(rd, samples):
+    """rspt_camera_rays: the device's generate_ray_differential over CameraSamples (n, 5) = p_film.xy, time, p_lens.xy -> (n, 22) = weight, o, d, t_max, time,
+    rx_o, rx_d, ry_o, ry_d, has_diff (world space, unscaled).  Needs init()."""
+    smp = np.ascontiguousarray(samples, np.float32).reshape(-1, 5)
+    out = np.zeros((len(smp), 22), np.float32)
+    _check(lib().rspt_camera_rays(C.addressof(rd), smp.ctypes.data, len(smp), out.ctypes.data))
+    return out
 
 
 def motion_bounds(start_m, start_time, end_m, end_time, box_min, box_max):

@@ -1135,15 +1135,43 @@ def gaussian_filter_table(radius=(2.0, 2.0), alpha=2.0):  # filters/gaussian.rs:
     return t
 
 
+def read_lens_file(path):
+    """read_float_file (floatfile.rs): whitespace-separated numbers, # to the end of the line is a comment -> (n, 4) f32"""
+    vals = []
+    for line in open(path):
+        vals += [float(v) for v in line.split("#", 1)[0].split()]
+    assert vals and len(vals) % 4 == 0, "Excess values in lens specification file %s; must be multiple-of-four values, read %d." % (path, len(vals))
+    return np.asarray(vals, F32).reshape(-1, 4)
+
+
+_REALISTIC_TABLES = {}
+
+
+def realistic_camera_tables(lens, aperture_diameter, focus_distance, film_diagonal, n_bounds=64):
+    """(elements LENS_ELEMENT_DT[n], exit pupil bounds (n_bounds, 4)) of rspt_realistic_camera_setup, cached per argument tuple within the process (the
+    64 x 1024^2 exit-pupil samples take seconds)"""
+    from . import lib
+    data = read_lens_file(lens) if isinstance(lens, (str, bytes, os.PathLike)) else np.ascontiguousarray(lens, F32).reshape(-1, 4)
+    key = (data.tobytes(), float(F32(aperture_diameter)), float(F32(focus_distance)), float(F32(film_diagonal)), int(n_bounds))
+    if key not in _REALISTIC_TABLES:
+        _REALISTIC_TABLES[key] = lib.realistic_camera_setup(data, aperture_diameter, focus_distance, film_diagonal, n_bounds)
+    return _REALISTIC_TABLES[key]
+
+
 def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.0, light_strategy=abi.LIGHTS_SPATIAL,
                      crop=(0.0, 1.0, 0.0, 1.0), filter_radius=(0.5, 0.5), filter_table=None, lens_radius=0.0,
                      focal_distance=1e6, max_sample_luminance=float("inf"), shard=(0, 1, 64), sampler="sobol",
                      sample_at_pixel_center=False, integrator="path", ao_samples=64, ao_cos_sample=True, direct_strategy="all", light_samples=None,
                      dimensions=4, strat=(4, 4), jitter=True, sample_range=None, allow_slow_paths=True, look_at_end=None, camera_times=(0.0, 1.0),
-                     shutter=(0.0, 1.0), mirror_x=False, camera="perspective", screen_window=None):
-    """camera: "perspective" | "orthographic" | "environment" (rspt_render_desc.camera_kind, ABI 25).  `fov` is read by the perspective camera only;
+                     shutter=(0.0, 1.0), mirror_x=False, camera="perspective", screen_window=None, lens=None, aperture_diameter=1.0, focus_distance=10.0,
+                     film_diagonal=35.0, simple_weighting=True):
+    """camera: "perspective" | "orthographic" | "environment" | "realistic" (rspt_render_desc.camera_kind).  `fov` is read by the perspective camera only;
     screen_window (x0, x1, y0, y1) is the "screenwindow" parameter, default that of the cameras' create() (the frame's aspect ratio around 0); the
     environment camera reads neither, nor the lens.
+    "realistic" (ABI 26; RealisticCamera::create, realistic.rs:145-197): lens = the lens file's numbers as an (n, 4) array or the path of such a file (rows
+    curvature radius, thickness, eta, aperture diameter in mm, front to back; # starts a comment), aperture_diameter ("aperturediameter", mm),
+    focus_distance ("focusdistance"), film_diagonal (Film "diagonal", mm), simple_weighting ("simpleweighting").  The element and exit-pupil tables come from
+    rspt_realistic_camera_setup, once per argument tuple and process; the desc keeps them alive.  fov, lens_radius and focal_distance are ignored.
     allow_slow_paths: True here (tests and bench want the device path whatever its speed); the Rust shim passes 0, so that a pixel-sampler
     frame of few tiles — which the device renders slower than the host's tile loop — comes back as RSPT_E_UNSUPPORTED (include/rspt.h)"""
     rd = abi.RenderDesc()
@@ -1178,7 +1206,14 @@ def make_render_desc(xres, yres, spp, look_at, fov, max_depth=5, rr_threshold=1.
         sw = (F32(-1), F32(1), F32(-1) / frame, F32(1) / frame)
     if screen_window is not None:
         sw = tuple(F32(v) for v in screen_window)
-    rd.camera_kind = {"perspective": abi.CAMERA_PERSPECTIVE, "orthographic": abi.CAMERA_ORTHOGRAPHIC, "environment": abi.CAMERA_ENVIRONMENT}[camera]
+    rd.camera_kind = {"perspective": abi.CAMERA_PERSPECTIVE, "orthographic": abi.CAMERA_ORTHOGRAPHIC, "environment": abi.CAMERA_ENVIRONMENT,
+                      "realistic": abi.CAMERA_REALISTIC}[camera]
+    if camera == "realistic":
+        rd._lens_elements, rd._exit_pupil_bounds = realistic_camera_tables(lens, aperture_diameter, focus_distance, film_diagonal)   # kept alive by the desc object
+        rd.lens_elements, rd.n_lens_elements = rd._lens_elements.ctypes.data, len(rd._lens_elements)
+        rd.exit_pupil_bounds, rd.n_exit_pupil_bounds = rd._exit_pupil_bounds.ctypes.data, len(rd._exit_pupil_bounds)
+        rd.film_diagonal = float(F32(film_diagonal) * F32(0.001))   # Film::new (film.rs:214)
+        rd.lens_simple_weighting = int(bool(simple_weighting))
     # OrthographicCamera::new orthographic.rs:50-70: camera_to_screen = Transform::orthographic(0, 1); the rest is the ProjectiveCamera set-up shared with the
     # perspective camera.  The environment camera has no projection: the field keeps the perspective matrix, which the library does not read.
     cam2screen = Transform.orthographic(0.0, 1.0) if camera == "orthographic" else Transform.perspective(fov, 1e-2, 1000.0)

@@ -1,13 +1,15 @@
-//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 25) one to one.
+//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 26) one to one.
 //! Uncompiled source for a maintainer (the image this repo is built in has no Rust toolchain); struct layouts are checked
 //! from the C side by tests/test_abi.py, so a mismatch here shows up as a wrong `size_of` against the table in INTEGRATION.md §2.
 #![allow(dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RSPT_ABI_VERSION: c_int = 25;
+pub const RSPT_ABI_VERSION: c_int = 26;
 pub const RSPT_CAMERA_PERSPECTIVE: u32 = 0;   // ABI 25: rspt_render_desc.camera_kind
 pub const RSPT_CAMERA_ORTHOGRAPHIC: u32 = 1;
 pub const RSPT_CAMERA_ENVIRONMENT: u32 = 2;
+pub const RSPT_CAMERA_REALISTIC: u32 = 3;     // ABI 26
+pub const RSPT_MAX_LENS_ELEMENTS: u32 = 32;
 pub const RSPT_MESH_INSTANCE: u32 = 0xffff_ffff;
 pub const RSPT_MESH_SPHERE: u32 = 0xffff_fffe;   // ABI 23: v[0] = index into spheres
 pub const RSPT_NO_MATERIAL: u32 = 0xffff_ffff;
@@ -60,6 +62,9 @@ pub struct RsptInstance { pub object: u32, pub to_world: [f32; 16], pub from_wor
     pub n_top_nodes: u64, pub n_top_prims: u64, pub instancing_mode: u32, pub n_media: u32, pub media: *const RsptMedium,
     pub spheres: *const RsptSphere, pub n_spheres: u32, pub pad_spheres: u32,   // ABI 23
 }
+/// rspt_lens_element (ABI 26): realistic.rs:27-33 LensElementInterface, metres
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct RsptLensElement { pub curvature_radius: f32, pub thickness: f32, pub eta: f32, pub aperture_radius: f32 }   // 16 B
 #[repr(C)] pub struct RsptSamplerTables { pub sobol32: *const u32, pub vdc: *const u64, pub vdc_inv: *const u64,
                                             pub halton_perms: *const u16, pub n_halton_perms: u64 }
 #[repr(C)] pub struct RsptRenderDesc {
@@ -73,7 +78,9 @@ pub struct RsptInstance { pub object: u32, pub to_world: [f32; 16], pub from_wor
     pub strat_x: u32, pub strat_y: u32, pub strat_jitter: u32, pub allow_slow_paths: u32, pub maxmin_c_pixel: *const u32,   // pixel samplers
     pub sample_begin: u64, pub sample_count: u64,   // checkpoint / resume: 0, 0 = the whole frame
     pub camera_animated: u32, pub camera_to_world_end: [f32; 16], pub camera_time: [f32; 2],   // AnimatedTransform camera (transform.rs:894-2124)
-    pub camera_kind: u32,   // ABI 25: RSPT_CAMERA_* (in what was the tail padding: size_of stays 1456)
+    pub camera_kind: u32,   // ABI 25: RSPT_CAMERA_* (in what was the tail padding)
+    pub lens_elements: *const RsptLensElement, pub n_lens_elements: u32, pub exit_pupil_bounds: *const f32, pub n_exit_pupil_bounds: u32,   // ABI 26: RealisticCamera
+    pub film_diagonal: f32, pub lens_simple_weighting: u32,
 }
 #[repr(C)] #[derive(Default)]
 pub struct RsptStats {

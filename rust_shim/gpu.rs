@@ -386,8 +386,13 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
     // ---- camera / film / sampler (perspective.rs:22-43, film.rs:159-173, sobol.rs:15-20, halton.rs:54-78) ----
     // ABI 25: the perspective, orthographic and environment cameras are served (rspt_render_desc.camera_kind); each fills the description from its own
     // fields.  The environment camera has no projection and no lens: the library reads full_res, the shutter and camera_to_world only.
+    // ABI 26: the realistic camera goes over as the state RealisticCamera::new built — element_interfaces (already focused), exit_pupil_bounds,
+    // simple_weighting, film.diagonal, all pub (realistic.rs:36-47, film.rs:163) — and is served by path and ao under the Sobol' / Halton samplers.
     struct CamDesc { kind: u32, raster_to_camera: [f32; 16], camera_to_world: crate::core::transform::AnimatedTransform, lens_radius: Float, focal_distance: Float,
                      shutter_open: Float, shutter_close: Float, film: Arc<crate::core::film::Film> }
+    let mut lens_elements: Vec<RsptLensElement> = Vec::new();
+    let mut exit_pupil_bounds: Vec<f32> = Vec::new();
+    let mut lens_simple_weighting = 0u32;
     let cam = match &*integ.get_camera() {
         Camera::Perspective(c) => { let c = c.clone_for_shim();
             CamDesc { kind: RSPT_CAMERA_PERSPECTIVE, raster_to_camera: m16(&c.raster_to_camera.m), camera_to_world: c.camera_to_world, lens_radius: c.lens_radius,
@@ -398,8 +403,21 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         Camera::Environment(c) =>                                                     // environment.rs:17-26
             CamDesc { kind: RSPT_CAMERA_ENVIRONMENT, raster_to_camera: m16(&Transform::default().m), camera_to_world: c.camera_to_world, lens_radius: 0.0,
                       focal_distance: 0.0, shutter_open: c.shutter_open, shutter_close: c.shutter_close, film: c.film.clone() },
-        Camera::Realistic(_) => return Err("camera is realistic (lens files, exit-pupil tables): not served on the device".into()),
+        Camera::Realistic(c) => {                                                     // realistic.rs:36-47
+            if c.element_interfaces.is_empty() || c.element_interfaces.len() > RSPT_MAX_LENS_ELEMENTS as usize {
+                return Err(format!("camera is realistic with {} lens interfaces: the device serves 1 to {}", c.element_interfaces.len(), RSPT_MAX_LENS_ELEMENTS));
+            }
+            for e in &c.element_interfaces {
+                lens_elements.push(RsptLensElement { curvature_radius: e.curvature_radius, thickness: e.thickness, eta: e.eta, aperture_radius: e.aperture_radius });
+            }
+            for b in &c.exit_pupil_bounds { exit_pupil_bounds.extend_from_slice(&[b.p_min.x, b.p_min.y, b.p_max.x, b.p_max.y]); }
+            lens_simple_weighting = c.simple_weighting as u32;
+            CamDesc { kind: RSPT_CAMERA_REALISTIC, raster_to_camera: m16(&Transform::default().m), camera_to_world: c.camera_to_world, lens_radius: 0.0,
+                      focal_distance: 0.0, shutter_open: c.shutter_open, shutter_close: c.shutter_close, film: c.film.clone() } }
     };
+    if cam.kind == RSPT_CAMERA_REALISTIC && integrator_kind > 1 {
+        return Err("camera is realistic under volpath / directlighting / whitted: the device serves it under path and ao only".into());
+    }
     // a moving camera goes over as its two key matrices and their times; the library decomposes and interpolates (AnimatedTransform::interpolate)
     let cam_anim = cam.camera_to_world.is_animated();                               // getter: rs_pbrt.patch (actually_animated)
     let film = cam.film.clone();
@@ -420,6 +438,7 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         _ => return Err("MLT sampler".into()),
     };
     if sampler_kind >= 3 && integrator_kind != 0 { return Err("pixel sampler with an integrator other than path".into()); }
+    if sampler_kind >= 3 && cam.kind == RSPT_CAMERA_REALISTIC { return Err("camera is realistic under a pixel sampler: the device serves it with sobol and halton only".into()); }
     let mut vdc = vec![0u64; 25 * 52]; let mut vdc_inv = vec![0u64; 26 * 52];       // rows zero-padded to 52 entries
     for (i, row) in VD_C_SOBOL_MATRICES.iter().enumerate() { vdc[i * 52..i * 52 + row.len()].copy_from_slice(row); }
     for (i, row) in VD_C_SOBOL_MATRICES_INV.iter().enumerate() { vdc_inv[i * 52..i * 52 + row.len()].copy_from_slice(row); }
@@ -443,6 +462,9 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         camera_animated: cam_anim as u32, camera_to_world_end: m16(&cam.camera_to_world.end_transform().m),
         camera_time: [cam.camera_to_world.start_time(), cam.camera_to_world.end_time()],
         camera_kind: cam.kind,
+        lens_elements: if lens_elements.is_empty() { std::ptr::null() } else { lens_elements.as_ptr() }, n_lens_elements: lens_elements.len() as u32,
+        exit_pupil_bounds: if exit_pupil_bounds.is_empty() { std::ptr::null() } else { exit_pupil_bounds.as_ptr() }, n_exit_pupil_bounds: (exit_pupil_bounds.len() / 4) as u32,
+        film_diagonal: film.diagonal, lens_simple_weighting,
     };
     let sd = RsptSceneDesc {
         nodes: f.nodes.as_ptr(), n_nodes: f.nodes.len() as u64, prims: f.prims.as_ptr(), n_prims: f.prims.len() as u64,
