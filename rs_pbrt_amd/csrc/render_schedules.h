@@ -43,27 +43,28 @@ int RenderRun::tune_any(uint32_t batch_n, TraceCall c) {
     if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: shadow rays of this scene: k_trace_w4<any> %.2f ms, k_trace_w4q %.2f ms on the same launch -> %s\n", ms_plain, ms_q, s->any_q_choice ? "the quantised records" : "the plain records");
     return 1;
 }
-// Which kernel serves this scene's camera-ray launches (trace_packet.h; launch_trace_v): measured once per scene, by the first camera launch of >= 2^22 rays of a path render —
-// both kernels run on the same rays (their hit records are identical, and the launch only writes them), the faster one is kept in rspt_scene_s::camera_pk_choice.
+// Which kernel serves this scene's camera-ray launches (trace_packet.h, trace_frustum.h; launch_trace_v): measured once per scene, by the first camera launch of >= 2^22 rays of a
+// path render — the three kernels run on the same rays (their hit records are identical, and the launch only writes them), the fastest one is kept in rspt_scene_s::camera_pk_choice.
 // RSPT_CAMERA_PACKET_TUNE=0 skips the measurement (the scene stays on k_trace_w4).  Returns as tune_any does.
 int RenderRun::tune_camera(uint32_t batch_n, TraceCall c) {
     if (s->camera_pk_choice >= 0 || getenv("RSPT_CAMERA_PACKET") || counters || d->integrator != RSPT_INTEGRATOR_PATH || batch_n < (1u << 22) || env_size("RSPT_CAMERA_PACKET_TUNE", 1) == 0) return 0;
     if (!camera_packet_ok(s, env_size("RSPT_TRACE_KERNEL", 2), (c.xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? c.xcd_cursors : nullptr)) return 0;
-    hipEvent_t t0 = get_event(n_ev++), t1 = get_event(n_ev++), t2 = get_event(n_ev++);
-    if (hipEventRecord(t0, g.stream) != hipSuccess) return RSPT_E_HIP;
-    c.force_camera_pk = 0;
-    launch_trace<false, 0>(tgrid, s, c);
-    (void)hipEventRecord(t1, g.stream);
-    (void)hipMemsetAsync(c.cursor, 0, sizeof(uint32_t), g.stream);   // (the persistent kernel's fetch cursor: the second run starts over)
-    c.force_camera_pk = 1;
-    launch_trace<false, 0>(tgrid, s, c);
-    (void)hipEventRecord(t2, g.stream);
-    if (hipEventSynchronize(t2) != hipSuccess) return RSPT_E_HIP;
-    float ms_w4 = 0.0f, ms_pk = 0.0f;
-    (void)hipEventElapsedTime(&ms_w4, t0, t1);
-    (void)hipEventElapsedTime(&ms_pk, t1, t2);
-    s->camera_pk_choice = ms_pk < ms_w4 ? 1 : 0;
-    if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: camera rays of this scene: k_trace_w4 %.2f ms, k_trace_w4pk %.2f ms on the same launch -> %s\n", ms_w4, ms_pk, s->camera_pk_choice ? "64-ray packets" : "per-lane walks");
+    hipEvent_t t[4] = {get_event(n_ev++), get_event(n_ev++), get_event(n_ev++), get_event(n_ev++)};
+    if (hipEventRecord(t[0], g.stream) != hipSuccess) return RSPT_E_HIP;
+    for (int k = 0; k < 3; k++) {
+        if (k) (void)hipMemsetAsync(c.cursor, 0, sizeof(uint32_t), g.stream);   // (the persistent kernel's fetch cursor: the next run starts over)
+        c.force_camera_pk = k;
+        launch_trace<false, 0>(tgrid, s, c);
+        (void)hipEventRecord(t[k + 1], g.stream);
+    }
+    if (hipEventSynchronize(t[3]) != hipSuccess) return RSPT_E_HIP;
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&ms[k], t[k], t[k + 1]);
+    int pick = 0;
+    for (int k = 1; k < 3; k++) if (ms[k] < ms[pick]) pick = k;
+    s->camera_pk_choice = pick;
+    static const char* const names[3] = {"per-lane walks", "64-ray packets", "64-ray packets, one frustum test per record"};
+    if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: camera rays of this scene: k_trace_w4 %.2f ms, k_trace_w4pk %.2f ms, k_trace_w4pf %.2f ms on the same launch -> %s\n", ms[0], ms[1], ms[2], names[pick]);
     return 1;
 }
 int RenderRun::batch_volpath(const Batch& bt, uint32_t& it) {  // VolPathIntegrator::li (vol.h): the continuation queue doubles as the list of live paths

@@ -47,15 +47,28 @@ RDEV uint2 pk_load2(const uint2* p) {
     return make_uint2(v.x, v.y);
 }
 
-template <int OUT_MODE>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                              const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                              float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
-                                                              uint32_t chunk /* rays a wave claims per global atomic (a multiple of 64; bit 0 as in trace_w4.h) */,
-                                                              const float4* __restrict__ leaf_boxes) {
-    __shared__ uint4 stack_s[RSPT_PK_WAVES * RSPT_W4_MAX_STACK];   // (ref, mask low, mask high, unused)
-    uint4* stk = stack_s + (threadIdx.x >> 6) * RSPT_W4_MAX_STACK;
+#ifdef RSPT_PK_COUNT   // timing-only A/B build (tools/ab_build.sh AB_DEFS=-DRSPT_PK_COUNT): records fetched, leaves tested, packets walked, summed per kernel family
+static __device__ unsigned long long g_pk_count[3];   // one copy per translation unit: read where the kernels are instantiated (tu_w4pk.hip / tu_w4pf.hip)
+#define RSPT_PK_COUNT_ADD(i) do { if (__lane_id() == 0) atomicAdd(&g_pk_count[i], 1ull); } while (0)
+#else
+#define RSPT_PK_COUNT_ADD(i) do { } while (0)
+#endif
+
+// k_trace_w4pk walks every sign group with the masked walk below
+struct PkMaskedOnly {
+    static constexpr bool frustum = false;
+    template <class LeafPhase, class LeafRange>
+    static RDEV bool walk(const Wide4Node*, const float4*, float4, float4, uint32_t, uint2*, uint32_t, uint32_t, uint64_t, float, float, float, float, float, float, float&, LeafPhase&, LeafRange&) { return false; }
+};
+
+// The body of the packet kernels.  FR::frustum: a sign group without the literal-chain bit is offered to FR::walk (trace_frustum.h) first; the masked walk serves the groups it declines.
+template <int OUT_MODE, class FR>
+RDEV void pk_trace_body(uint4* stk, const SceneDev& sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
+                        const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
+                        const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
+                        float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
+                        uint32_t chunk /* rays a wave claims per global atomic (a multiple of 64; bit 0 as in trace_w4.h) */,
+                        const float4* __restrict__ leaf_boxes) {
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     {   // a short queue is spread over all waves (trace_w4.h: the claim shrinks to the queue's share per wave)
         const bool adapt = !(chunk & 1u);
@@ -109,6 +122,7 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(Scene
 
         // ---- the packet's sign groups, one walk each ----
         uint64_t todo = __ballot(alive);
+        if (todo) RSPT_PK_COUNT_ADD(2);
         while (todo) {
             const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)negbits, (int)(__ffsll((unsigned long long)todo) - 1));   // wave-uniform
             const uint64_t gmask = __ballot(alive && negbits == nb);
@@ -140,6 +154,9 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(Scene
                 *offset = off; *n_prims = np;
             };
 
+            if (FR::frustum && !(nb & 8u) &&
+                FR::walk(recs, leaf_boxes, root0, root1, root_ref, reinterpret_cast<uint2*>(stk), lane, nb, gmask, ox, oy, oz, ix, iy, iz, t_max, leaf_phase, leaf_range))
+                continue;   // (false: the group's rays are not a narrow bundle, and nothing was walked)
             for (;;) {
                 if (cur == RSPT_NONE) {
                     if (sp == 0) break;
@@ -154,19 +171,21 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(Scene
                         const float4 q0 = pk_load4(leaf_boxes + 2 * (size_t)offset), q1 = pk_load4(leaf_boxes + 2 * (size_t)offset + 1);
                         const bool ok = ((mask >> lane) & 1ull) != 0 && box_hit(q0, q1, f3{ox, oy, oz}, f3{ix, iy, iz}, n0, n1, n2, t_max);
                         const uint64_t lmask = __ballot(ok);
+                        RSPT_PK_COUNT_ADD(1);
                         if (lmask) leaf_phase(offset, n_prims, lmask);
                         continue;
                     }
                     cur = ref;
                 }
                 // ---- node step: one record for the lanes of mask ----
+                RSPT_PK_COUNT_ADD(0);
                 const float4* pp = reinterpret_cast<const float4*>(recs + cur);
                 const float4 a0 = pk_load4(pp), a1 = pk_load4(pp + 1), a2 = pk_load4(pp + 2), a3 = pk_load4(pp + 3), a4 = pk_load4(pp + 4), a5 = pk_load4(pp + 5), rf = pk_load4(pp + 6);
                 cur = RSPT_NONE;
                 const bool in = ((mask >> lane) & 1ull) != 0;
                 bool h0, h1, h2, h3;
                 float m0, m1, m2, m3;
-                if (!(nb & 8u)) {
+                if (!FR::frustum && !(nb & 8u)) {   // (under FR::frustum only the literal-chain groups and the wide ones FR::walk declined come here, and take the reference's chain: the pair arm and its registers fold away)
                     box_pair_hit_m(a0, a1, a2, ox, oy, oz, ix, iy, iz, t_max, &h0, &h1, &m0, &m1);
                     __builtin_amdgcn_sched_barrier(0);   // (one pair after the other: interleaved, the two cost ten more registers and a wave of occupancy)
                     box_pair_hit_m(a3, a4, a5, ox, oy, oz, ix, iy, iz, t_max, &h2, &h3, &m2, &m3);
@@ -226,6 +245,17 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(Scene
             }
         }
     }
+}
+
+template <int OUT_MODE>
+__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
+                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
+                                                              const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
+                                                              float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
+                                                              uint32_t chunk, const float4* __restrict__ leaf_boxes) {
+    __shared__ uint4 stack_s[RSPT_PK_WAVES * RSPT_W4_MAX_STACK];   // (ref, mask low, mask high, unused)
+    pk_trace_body<OUT_MODE, PkMaskedOnly>(stack_s + (threadIdx.x >> 6) * RSPT_W4_MAX_STACK, sc, recs, big_leaves, root_ref, queue, count_ptr, count_imm, cursor, rays_a, rays_b, out_a, out_b, out_hits,
+                                          chunk, leaf_boxes);
 }
 
 }  // namespace rspt

@@ -8,6 +8,7 @@
 #include "trace_w4.h"
 #include "trace_w4q.h"
 #include "trace_packet.h"
+#include "trace_frustum.h"
 
 namespace rspt {
 
@@ -180,6 +181,12 @@ RSPT_TU_X template __global__ void k_trace_w4q<1>(SceneDev, const Quad4Node*, co
     RSPT_TU_X template __global__ void k_trace_w4pk<OM>(SceneDev, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, \
                                                         rspt_hit*, uint32_t, const float4*);
 RSPT_TU_W4PK(0) RSPT_TU_W4PK(1)   /* the packet walk of coherent closest-hit launches (trace_packet.h): the render's queues, the trace hook */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4PF)
+#define RSPT_TU_W4PF(OM) \
+    RSPT_TU_X template __global__ void k_trace_w4pf<OM>(SceneDev, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, \
+                                                        rspt_hit*, uint32_t, const float4*);
+RSPT_TU_W4PF(0) RSPT_TU_W4PF(1)   /* the packet walk with one frustum test per record (trace_frustum.h): the render's queues, the trace hook */
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4)
 RSPT_TU_W4_4(false, 0) RSPT_TU_W4_4(false, 1) RSPT_TU_W4_4(true, 0) RSPT_TU_W4_4(true, 1)

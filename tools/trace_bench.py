@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the traversal stage through rspt_trace_device on the C2 soup:
 coherent camera rays (one per pixel, and "pixel": 64 jittered rays per pixel — what a wave of a render's camera launch holds), incoherent interior rays;
-closest- and any-hit.  Every closest-hit set is also timed with the packet kernel (csrc/trace_packet.h, RSPT_CAMERA_PACKET=1); --check holds it to the
-reference-order kernel's records."""
+closest- and any-hit.  Every closest-hit set is also timed with the packet kernel (csrc/trace_packet.h, RSPT_CAMERA_PACKET=1) and the frustum packet kernel
+(csrc/trace_frustum.h, RSPT_CAMERA_PACKET=2); --check holds both to the reference-order kernel's records."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -59,10 +59,11 @@ for name, rays in sets.items():
             extra = " identical=%s" % (got.tobytes() == ref.tobytes())
         gb = (32.0 * nodes + 48.0 * tris + (72 if any_hit else 96) * len(rays)) / 1e9
         print(f"{name:11s} any={int(any_hit)} rays={len(rays)} {ms:8.3f} ms  {len(rays) / ms / 1e3:8.1f} Mrays/s  nodes/ray {nodes / len(rays):6.1f} tris/ray {tris / len(rays):5.2f}  alg {gb / ms * 1e3:7.1f} GB/s{extra}", flush=True)
-        if not any_hit:   # the packet kernel on the same rays (incoherent ones are slow there, and must still be right)
-            os.environ["RSPT_CAMERA_PACKET"] = "1"
-            ms_pk = lib.trace_device(ds, rb, len(rays), hb, any_hit=False, repeat=args.repeat)
-            del os.environ["RSPT_CAMERA_PACKET"]
-            extra = " identical=%s" % (hb.download(abi.HIT_DT, len(rays)).tobytes() == ref.tobytes()) if args.check else ""
-            print(f"{name:11s} packet rays={len(rays)} {ms_pk:8.3f} ms  {len(rays) / ms_pk / 1e3:8.1f} Mrays/s  ({ms / ms_pk:5.2f} x k_trace_w4){extra}", flush=True)
+        if not any_hit:   # the two packet kernels on the same rays (incoherent ones are slow there, and must still be right)
+            for label, value in (("packet", "1"), ("frustum", "2")):
+                os.environ["RSPT_CAMERA_PACKET"] = value
+                ms_pk = lib.trace_device(ds, rb, len(rays), hb, any_hit=False, repeat=args.repeat)
+                del os.environ["RSPT_CAMERA_PACKET"]
+                extra = " identical=%s" % (hb.download(abi.HIT_DT, len(rays)).tobytes() == ref.tobytes()) if args.check else ""
+                print(f"{name:11s} {label:7s} rays={len(rays)} {ms_pk:8.3f} ms  {len(rays) / ms_pk / 1e3:8.1f} Mrays/s  ({ms / ms_pk:5.2f} x k_trace_w4){extra}", flush=True)
     rb.free(); hb.free()
