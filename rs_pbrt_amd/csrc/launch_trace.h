@@ -41,7 +41,7 @@ struct TraceCall {
     bool count = false;                // the reference-order kernel with its node / triangle counters
     bool camera_launch = false;        // the camera rays of a batch (a pixel-major queue): RSPT_PW_CHUNK_CAMERA / _REFILL_CAMERA / _LEAF_CAMERA
     int force_any_q = -1;              // tune_any's measurement of the two shadow-ray kernels: 0 / 1 forces the plain / the quantised one
-    int force_camera_pk = -1;          // tune_camera's measurement of the three camera-ray kernels: 0 / 1 / 2 forces k_trace_w4 / the packet kernel / the frustum packet kernel
+    int force_camera_pk = -1;          // tune_camera's measurement of the camera-ray kernels: 0 / 1 / 2 / 3 / 4 forces k_trace_w4 / the packet kernel / the frustum packet kernel / its bundles of two / of four packets
     uint32_t* inst_out = nullptr;      // where a closest-hit launch records the instance of each hit instead of g.hit_inst (volpath's shadow-ray segments)
     uint32_t queue_hint = 0xffffffffu; // upper bound of the queue's length when the host knows one (hinted_grid), 0xffffffff: none
 };
@@ -68,14 +68,26 @@ bool camera_packet_ok(const rspt_scene_s* s, size_t which, const uint32_t* xcur)
     return which >= 2 && s->w4_ok && s->w4 && s->leaf_boxes && !s->has_instances && !s->has_alpha && !s->has_spheres && !(s->w4_root & RSPT_REF_LEAF) &&
            env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) == 0 && !xcur;
 }
-// which kernel a closest-hit launch asks for: 0 = k_trace_w4, 1 = k_trace_w4pk (trace_packet.h), 2 = k_trace_w4pf (trace_frustum.h)
+// which kernel a closest-hit launch asks for: 0 = k_trace_w4, 1 = k_trace_w4pk (trace_packet.h), 2 = k_trace_w4pf (trace_frustum.h), 3 / 4 = k_trace_w4pb with bundles of
+// two / four packets (trace_bundle.h)
 int camera_packet_wanted(const rspt_scene_s* s, const TraceCall& c) {
     int v;
     const char* e = getenv("RSPT_CAMERA_PACKET");
     if (c.force_camera_pk >= 0) v = c.force_camera_pk;
     else if (e && *e) v = atoi(e);
     else v = c.camera_launch ? s->camera_pk_choice : 0;
-    return v <= 0 ? 0 : (v == 2 ? 2 : 1);
+    return v <= 0 ? 0 : (v >= 2 && v <= 4 ? v : 1);
+}
+// workgroups per CU of a bundle kernel: what its registers allow (a workgroup is one wave per SIMD), asked of the runtime once per instantiation
+template <int OUT_MODE, int R>
+uint32_t bundle_blocks_per_cu() {
+    static int blocks = 0;
+    if (blocks == 0) {
+        int b = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<const void*>(k_trace_w4pb<OUT_MODE, R>), RSPT_PW_BLOCK, 0) != hipSuccess) { (void)hipGetLastError(); b = 0; }
+        blocks = std::min(std::max(b, 1), 8);
+    }
+    return (uint32_t)blocks;
 }
 template <bool ANY, int OUT_MODE, bool INST, bool ALPHA>
 void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur) {
@@ -134,10 +146,21 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
     }
     if constexpr (!ANY && !INST && !ALPHA) {
         // The camera rays of a batch (a pixel-major queue: the 64 lanes of a wave hold samples of one pixel) walk the tree as 64-ray packets (trace_packet.h): records and
-        // triangles fetched once per wave, one stack per wave.  Hit records byte-identical.  RSPT_CAMERA_PACKET=0 / 1 / 2 forces the old / the packet / the frustum packet kernel — 1 and 2 for EVERY
+        // triangles fetched once per wave, one stack per wave.  Hit records byte-identical.  RSPT_CAMERA_PACKET=0 / 1 / 2 / 3 / 4 forces the old / the packet / the frustum packet kernel / its bundle forms — 1 to 4 for EVERY
         // closest-hit launch that qualifies, the trace hook included (incoherent rays are slow there, and right); otherwise the scene's measured choice
         // (rspt_scene_s::camera_pk_choice) serves the camera launches, k_trace_w4 until it exists.
         const int pk = camera_packet_wanted(s, c);
+        if (pk >= 3 && camera_packet_ok(s, which, xcur)) {
+            // RSPT_CAMERA_PACKET=3 / 4: the frustum walk once per bundle of two / four packets (trace_bundle.h: with 128 / 256 or more samples per pixel a bundle is one pixel), same
+            // arguments, same records; the grid is what the kernel's registers allow
+            auto go = [&](auto kern, uint32_t per_cu) {
+                hipLaunchKernelGGL(kern, dim3(hinted_grid(c.queue_hint, grid_for(per_cu), RSPT_PW_BLOCK)), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr,
+                                   c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.hits, pw_chunk, s->leaf_boxes);
+            };
+            if (pk == 3) go(k_trace_w4pb<OUT_MODE, 2>, bundle_blocks_per_cu<OUT_MODE, 2>());
+            else go(k_trace_w4pb<OUT_MODE, 4>, bundle_blocks_per_cu<OUT_MODE, 4>());
+            return;
+        }
         if (pk && camera_packet_ok(s, which, xcur)) {
             // (no spill rows and 6 KB of LDS: its grid is its own — six workgroups per CU = the six waves per SIMD its 79 VGPRs allow; RSPT_PK_BLOCKS_PER_CU for A/B builds)
             const uint32_t kgrid = hinted_grid(c.queue_hint, grid_for((uint32_t)std::min<size_t>(std::max<size_t>(env_size("RSPT_PK_BLOCKS_PER_CU", 6), 1), 8)), RSPT_PW_BLOCK);

@@ -234,8 +234,8 @@ struct rspt_scene_s {
     bool w4_ok = false;               // false: too large for the ref fields, k_trace_pw serves the scene
     const Quad4Node* w4q = nullptr;   // the same records on an 8-bit grid, for the shadow-ray kernel k_trace_w4q (trace_w4q.h): plain scenes only (no instances, no alpha masks)
     const float4* leaf_boxes = nullptr;  // [2 * first primitive of a leaf]: the leaf's LinearBVHNode bounds, for that kernel's exact leaf test
-    int camera_pk_choice = -1;        // which kernel serves this scene's camera-ray launches: -1 not measured yet (k_trace_w4 until then), 0 k_trace_w4, 1 k_trace_w4pk (trace_packet.h), 2 k_trace_w4pf (trace_frustum.h) —
-                                      // set by the first large camera launch of a path render, which runs all three on the same rays and keeps the fastest (RenderRun::tune_camera)
+    int camera_pk_choice = -1;        // which kernel serves this scene's camera-ray launches: -1 not measured yet (k_trace_w4 until then), 0 k_trace_w4, 1 k_trace_w4pk (trace_packet.h), 2 k_trace_w4pf (trace_frustum.h), 3 / 4 k_trace_w4pb with bundles of two / four packets (trace_bundle.h) —
+                                      // set by the first large camera launch of a path render, which runs all five on the same rays and keeps the fastest (RenderRun::tune_camera)
     int any_q_choice = -1;            // which kernel serves this scene's shadow rays: -1 not measured yet (the plain one until then), 0 k_trace_w4<true>, 1 k_trace_w4q — set by
                                       // the first large shadow-ray launch of a render, which runs both on the same rays and keeps the faster (RenderRun::tune_any)
     TexTables tex{};                  // textures / images / per-material slots (dev_texture.h); has_textures says whether set

@@ -43,28 +43,33 @@ int RenderRun::tune_any(uint32_t batch_n, TraceCall c) {
     if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: shadow rays of this scene: k_trace_w4<any> %.2f ms, k_trace_w4q %.2f ms on the same launch -> %s\n", ms_plain, ms_q, s->any_q_choice ? "the quantised records" : "the plain records");
     return 1;
 }
-// Which kernel serves this scene's camera-ray launches (trace_packet.h, trace_frustum.h; launch_trace_v): measured once per scene, by the first camera launch of >= 2^22 rays of a
-// path render — the three kernels run on the same rays (their hit records are identical, and the launch only writes them), the fastest one is kept in rspt_scene_s::camera_pk_choice.
+// Which kernel serves this scene's camera-ray launches (trace_packet.h, trace_frustum.h, trace_bundle.h; launch_trace_v): measured once per scene, by the first camera launch of >= 2^22 rays of a
+// path render — the five candidates (four extra launches, once per scene) run on the same rays (their hit records are identical, and the launch only writes them), the fastest one is kept in rspt_scene_s::camera_pk_choice.
 // RSPT_CAMERA_PACKET_TUNE=0 skips the measurement (the scene stays on k_trace_w4).  Returns as tune_any does.
 int RenderRun::tune_camera(uint32_t batch_n, TraceCall c) {
     if (s->camera_pk_choice >= 0 || getenv("RSPT_CAMERA_PACKET") || counters || d->integrator != RSPT_INTEGRATOR_PATH || batch_n < (1u << 22) || env_size("RSPT_CAMERA_PACKET_TUNE", 1) == 0) return 0;
     if (!camera_packet_ok(s, env_size("RSPT_TRACE_KERNEL", 2), (c.xcd_cursors && env_size("RSPT_XCD_DEAL", 0) != 0) ? c.xcd_cursors : nullptr)) return 0;
-    hipEvent_t t[4] = {get_event(n_ev++), get_event(n_ev++), get_event(n_ev++), get_event(n_ev++)};
+    constexpr int NK = 5;
+    hipEvent_t t[NK + 1];
+    for (int k = 0; k <= NK; k++) t[k] = get_event(n_ev++);
     if (hipEventRecord(t[0], g.stream) != hipSuccess) return RSPT_E_HIP;
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < NK; k++) {
         if (k) (void)hipMemsetAsync(c.cursor, 0, sizeof(uint32_t), g.stream);   // (the persistent kernel's fetch cursor: the next run starts over)
         c.force_camera_pk = k;
         launch_trace<false, 0>(tgrid, s, c);
         (void)hipEventRecord(t[k + 1], g.stream);
     }
-    if (hipEventSynchronize(t[3]) != hipSuccess) return RSPT_E_HIP;
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&ms[k], t[k], t[k + 1]);
+    if (hipEventSynchronize(t[NK]) != hipSuccess) return RSPT_E_HIP;
+    float ms[NK] = {};
+    for (int k = 0; k < NK; k++) (void)hipEventElapsedTime(&ms[k], t[k], t[k + 1]);
     int pick = 0;
-    for (int k = 1; k < 3; k++) if (ms[k] < ms[pick]) pick = k;
+    for (int k = 1; k < NK; k++) if (ms[k] < ms[pick]) pick = k;
     s->camera_pk_choice = pick;
-    static const char* const names[3] = {"per-lane walks", "64-ray packets", "64-ray packets, one frustum test per record"};
-    if (getenv("RSPT_VERBOSE")) fprintf(stderr, "rspt: camera rays of this scene: k_trace_w4 %.2f ms, k_trace_w4pk %.2f ms, k_trace_w4pf %.2f ms on the same launch -> %s\n", ms[0], ms[1], ms[2], names[pick]);
+    static const char* const names[NK] = {"per-lane walks", "64-ray packets", "64-ray packets, one frustum test per record", "bundles of two packets, one frustum walk each",
+                                          "bundles of four packets, one frustum walk each"};
+    if (getenv("RSPT_VERBOSE"))
+        fprintf(stderr, "rspt: camera rays of this scene: k_trace_w4 %.2f ms, k_trace_w4pk %.2f ms, k_trace_w4pf %.2f ms, k_trace_w4pb<2> %.2f ms, k_trace_w4pb<4> %.2f ms on the same launch -> %s\n",
+                ms[0], ms[1], ms[2], ms[3], ms[4], names[pick]);
     return 1;
 }
 int RenderRun::batch_volpath(const Batch& bt, uint32_t& it) {  // VolPathIntegrator::li (vol.h): the continuation queue doubles as the list of live paths

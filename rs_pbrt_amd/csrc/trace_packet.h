@@ -61,41 +61,13 @@ struct PkMaskedOnly {
     static RDEV bool walk(const Wide4Node*, const float4*, float4, float4, uint32_t, uint2*, uint32_t, uint32_t, uint64_t, float, float, float, float, float, float, float&, LeafPhase&, LeafRange&) { return false; }
 };
 
-// The body of the packet kernels.  FR::frustum: a sign group without the literal-chain bit is offered to FR::walk (trace_frustum.h) first; the masked walk serves the groups it declines.
+// One packet of the packet kernels: lane by lane the queue entry qpos (where `valid`), loaded, walked and stored.  FR::frustum: a sign group without the literal-chain bit is offered to
+// FR::walk (trace_frustum.h) first; the masked walk serves the groups it declines.
 template <int OUT_MODE, class FR>
-RDEV void pk_trace_body(uint4* stk, const SceneDev& sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                        const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                        const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                        float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
-                        uint32_t chunk /* rays a wave claims per global atomic (a multiple of 64; bit 0 as in trace_w4.h) */,
-                        const float4* __restrict__ leaf_boxes) {
-    const uint32_t n = count_ptr ? *count_ptr : count_imm;
-    {   // a short queue is spread over all waves (trace_w4.h: the claim shrinks to the queue's share per wave)
-        const bool adapt = !(chunk & 1u);
-        chunk &= ~63u;
-        const uint32_t waves = gridDim.x * (uint32_t)RSPT_PK_WAVES;
-        uint32_t per = ((n + waves - 1u) / waves + 63u) & ~63u;
-        if (per < 64u) per = 64u;
-        if (adapt && per < chunk) chunk = per;
-    }
-    const uint32_t lane = __lane_id();
-    const float4 root0 = sc.nodes[0], root1 = sc.nodes[1];
-    uint32_t chunk_lo = 0, chunk_hi = 0;   // wave-uniform
-
-    for (;;) {
-        // ---- the next packet of the wave's claim ----
-        if (chunk_lo == chunk_hi) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(cursor, chunk);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base >= n) break;
-            chunk_lo = base;
-            chunk_hi = (n - base) > chunk ? base + chunk : n;
-        }
-        const uint32_t qpos = chunk_lo + lane;
-        const bool valid = qpos < chunk_hi;
-        chunk_lo = (chunk_hi - chunk_lo) > 64u ? chunk_lo + 64u : chunk_hi;
-
+RDEV void pk_trace_packet(uint4* stk, const SceneDev& sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref, const uint32_t* __restrict__ queue,
+                          const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b, float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
+                          const float4* __restrict__ leaf_boxes, float4 root0, float4 root1, uint32_t lane, uint32_t qpos, bool valid) {
+    {
         // ---- per-lane ray state: the expressions of k_trace_w4's refill block ----
         float ox = 0, oy = 0, oz = 0, ix = 0, iy = 0, iz = 0;
         RayShear rs{0, 0, 0, 0, 0, 0};
@@ -244,6 +216,44 @@ RDEV void pk_trace_body(uint4* stk, const SceneDev& sc, const Wide4Node* __restr
                 out_hits[qpos] = h;
             }
         }
+    }
+}
+
+// The body of the packet kernels: a wave claims runs of the queue and serves them packet by packet.
+template <int OUT_MODE, class FR>
+RDEV void pk_trace_body(uint4* stk, const SceneDev& sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
+                        const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
+                        const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
+                        float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
+                        uint32_t chunk /* rays a wave claims per global atomic (a multiple of 64; bit 0 as in trace_w4.h) */,
+                        const float4* __restrict__ leaf_boxes) {
+    const uint32_t n = count_ptr ? *count_ptr : count_imm;
+    {   // a short queue is spread over all waves (trace_w4.h: the claim shrinks to the queue's share per wave)
+        const bool adapt = !(chunk & 1u);
+        chunk &= ~63u;
+        const uint32_t waves = gridDim.x * (uint32_t)RSPT_PK_WAVES;
+        uint32_t per = ((n + waves - 1u) / waves + 63u) & ~63u;
+        if (per < 64u) per = 64u;
+        if (adapt && per < chunk) chunk = per;
+    }
+    const uint32_t lane = __lane_id();
+    const float4 root0 = sc.nodes[0], root1 = sc.nodes[1];
+    uint32_t chunk_lo = 0, chunk_hi = 0;   // wave-uniform
+
+    for (;;) {
+        // ---- the next packet of the wave's claim ----
+        if (chunk_lo == chunk_hi) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(cursor, chunk);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base >= n) break;
+            chunk_lo = base;
+            chunk_hi = (n - base) > chunk ? base + chunk : n;
+        }
+        const uint32_t qpos = chunk_lo + lane;
+        const bool valid = qpos < chunk_hi;
+        chunk_lo = (chunk_hi - chunk_lo) > 64u ? chunk_lo + 64u : chunk_hi;
+        pk_trace_packet<OUT_MODE, FR>(stk, sc, recs, big_leaves, root_ref, queue, rays_a, rays_b, out_a, out_b, out_hits, leaf_boxes, root0, root1, lane, qpos, valid);
     }
 }
 

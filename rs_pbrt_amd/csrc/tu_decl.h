@@ -9,6 +9,7 @@
 #include "trace_w4q.h"
 #include "trace_packet.h"
 #include "trace_frustum.h"
+#include "trace_bundle.h"
 
 namespace rspt {
 
@@ -187,6 +188,12 @@ RSPT_TU_W4PK(0) RSPT_TU_W4PK(1)   /* the packet walk of coherent closest-hit lau
     RSPT_TU_X template __global__ void k_trace_w4pf<OM>(SceneDev, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, \
                                                         rspt_hit*, uint32_t, const float4*);
 RSPT_TU_W4PF(0) RSPT_TU_W4PF(1)   /* the packet walk with one frustum test per record (trace_frustum.h): the render's queues, the trace hook */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4PB)
+#define RSPT_TU_W4PB(OM, R) \
+    RSPT_TU_X template __global__ void k_trace_w4pb<OM, R>(SceneDev, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, \
+                                                           rspt_hit*, uint32_t, const float4*);
+RSPT_TU_W4PB(0, 2) RSPT_TU_W4PB(1, 2) RSPT_TU_W4PB(0, 4) RSPT_TU_W4PB(1, 4)   /* the frustum walk for bundles of two / four packets per wave (trace_bundle.h) */
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4)
 RSPT_TU_W4_4(false, 0) RSPT_TU_W4_4(false, 1) RSPT_TU_W4_4(true, 0) RSPT_TU_W4_4(true, 1)

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the traversal stage through rspt_trace_device on the C2 soup:
-coherent camera rays (one per pixel, and "pixel": 64 jittered rays per pixel — what a wave of a render's camera launch holds), incoherent interior rays;
-closest- and any-hit.  Every closest-hit set is also timed with the packet kernel (csrc/trace_packet.h, RSPT_CAMERA_PACKET=1) and the frustum packet kernel
-(csrc/trace_frustum.h, RSPT_CAMERA_PACKET=2); --check holds both to the reference-order kernel's records."""
+coherent camera rays (one per pixel, "pixel": 64 jittered rays per pixel — what a wave of a render's camera launch holds — and "pixel256": 256 per pixel in queue
+order, what four consecutive waves of the headline's camera launch hold), incoherent interior rays; closest- and any-hit.  Every closest-hit set is also timed with the packet
+kernel (csrc/trace_packet.h, RSPT_CAMERA_PACKET=1), the frustum packet kernel (csrc/trace_frustum.h, RSPT_CAMERA_PACKET=2) and its bundle forms of two and four packets
+(csrc/trace_bundle.h, RSPT_CAMERA_PACKET=3 / 4); --check holds all four to the reference-order kernel's records."""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,6 +40,13 @@ py = np.repeat(((yy.reshape(-1) + 0.5) / side - 0.5) * 2 * half, 64) + rng.unifo
 dd = np.stack([px, py, np.ones_like(px)], 1); dd /= np.linalg.norm(dd, axis=1)[:, None]
 r = np.zeros(len(px), abi.RAY_DT); r["o"] = (0, 0, -4); r["d"] = dd.astype(np.float32); r["t_max"] = np.inf
 sets["pixel"] = r
+n_px = n // 256   # the headline's shape: 256 samples per pixel, so an aligned run of 256 queue entries is one pixel
+side = int(np.sqrt(n_px)); yy, xx = np.mgrid[0:side, 0:side]
+px = np.repeat(((xx.reshape(-1) + 0.5) / side - 0.5) * 2 * half, 256) + rng.uniform(0, 2 * half / 1024, side * side * 256)
+py = np.repeat(((yy.reshape(-1) + 0.5) / side - 0.5) * 2 * half, 256) + rng.uniform(0, 2 * half / 1024, side * side * 256)
+dd = np.stack([px, py, np.ones_like(px)], 1); dd /= np.linalg.norm(dd, axis=1)[:, None]
+r = np.zeros(len(px), abi.RAY_DT); r["o"] = (0, 0, -4); r["d"] = dd.astype(np.float32); r["t_max"] = np.inf
+sets["pixel256"] = r
 to_light = sets["incoherent"].copy()
 tgt = np.stack([rng.uniform(-.5, .5, n), np.full(n, 1.5), rng.uniform(-.5, .5, n)], 1).astype(np.float32)
 to_light["d"] = tgt - to_light["o"]; to_light["t_max"] = 0.9999
@@ -59,8 +67,8 @@ for name, rays in sets.items():
             extra = " identical=%s" % (got.tobytes() == ref.tobytes())
         gb = (32.0 * nodes + 48.0 * tris + (72 if any_hit else 96) * len(rays)) / 1e9
         print(f"{name:11s} any={int(any_hit)} rays={len(rays)} {ms:8.3f} ms  {len(rays) / ms / 1e3:8.1f} Mrays/s  nodes/ray {nodes / len(rays):6.1f} tris/ray {tris / len(rays):5.2f}  alg {gb / ms * 1e3:7.1f} GB/s{extra}", flush=True)
-        if not any_hit:   # the two packet kernels on the same rays (incoherent ones are slow there, and must still be right)
-            for label, value in (("packet", "1"), ("frustum", "2")):
+        if not any_hit:   # the packet kernels on the same rays (incoherent ones are slow there, and must still be right)
+            for label, value in (("packet", "1"), ("frustum", "2"), ("bundle2", "3"), ("bundle4", "4")):
                 os.environ["RSPT_CAMERA_PACKET"] = value
                 ms_pk = lib.trace_device(ds, rb, len(rays), hb, any_hit=False, repeat=args.repeat)
                 del os.environ["RSPT_CAMERA_PACKET"]
