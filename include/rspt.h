@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RSPT_ABI_VERSION 26
+#define RSPT_ABI_VERSION 27
 
 /* error codes */
 #define RSPT_OK 0
@@ -57,9 +57,11 @@ typedef struct {
 #define RSPT_MESH_INSTANCE 0xffffffffu /* rspt_prim.mesh of a TransformedPrimitive: v[0] = index into instances[] */
 #define RSPT_MESH_SPHERE 0xfffffffeu   /* rspt_prim.mesh of a GeometricPrimitive wrapping a Sphere (ABI 23): v[0] = index into spheres[],
                                           v[1] = v[2] = 0; material and area_light as for a triangle */
+#define RSPT_MESH_DISK 0xfffffffdu     /* ... wrapping a Disk (ABI 27): v[0] = index into disks[], v[1] = v[2] = 0 */
+#define RSPT_MESH_CYLINDER 0xfffffffcu /* ... wrapping a Cylinder (ABI 27): v[0] = index into cylinders[], v[1] = v[2] = 0 */
 typedef struct {
     uint32_t v[3];
-    uint32_t mesh;       /* index into meshes[], RSPT_MESH_INSTANCE or RSPT_MESH_SPHERE */
+    uint32_t mesh;       /* index into meshes[], RSPT_MESH_INSTANCE, RSPT_MESH_SPHERE, RSPT_MESH_DISK or RSPT_MESH_CYLINDER */
     uint32_t material;   /* index into materials[]; 0xffffffff = no material
                             (path.rs:109-116 passes straight through)               */
     int32_t area_light;  /* index into lights[] or -1 (primitive.rs:193-195)         */
@@ -101,6 +103,34 @@ typedef struct {
     uint32_t reverse_orientation, transform_swaps_handedness;
     uint32_t medium_inside, medium_outside; /* as in rspt_mesh: 0 = no medium, else 1 + index into media[] */
 } rspt_sphere; /* 168 B */
+
+/* ---- disks and cylinders (ABI 27): what Disk (src/shapes/disk.rs:17-28) and Cylinder (src/shapes/cylinder.rs:18-30) hold, one record per
+ * Shape "disk" / Shape "cylinder" ----
+ * The two Transform.m as for rspt_sphere.  Disk: height, radius, inner_radius as given, phi_max in radians as Disk::new left it
+ * (radians(clamp(phimax, 0, 360)), disk.rs:69).  Cylinder: radius as given, z_min / z_max after Cylinder::new's min / max (cylinder.rs:70-71),
+ * phi_max likewise in radians.  The library intersects them exactly as Disk::intersect / intersect_p (disk.rs:92-197: a plane test in plain
+ * f32, t >= t_max rejects) and Cylinder::intersect / intersect_p (cylinder.rs:95-320: the EFloat quadratic over x and y only, the z / phi
+ * clipping with the retry on t1).  Served as SURFACES exactly where spheres are: rspt_trace / rspt_trace_device, rspt_quadric_intersect,
+ * rspt_render under RSPT_INTEGRATOR_PATH and RSPT_INTEGRATOR_AO with the Sobol' / Halton samplers, rspt_light_distribution while no disk or
+ * cylinder is a light.  rspt_render answers RSPT_E_UNSUPPORTED ("disk" / "cylinder", whichever the scene holds, and what is missing) for an
+ * emissive one ("disk area light" / "cylinder area light"; rspt_light_distribution answers the same), the directlighting / whitted / volpath
+ * integrators, the pixel samplers, a projection or goniometric light beside them, the on-demand light table, more four-box records than a
+ * reference holds, and RSPT_COUNTERS.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED): disks or cylinders together with object
+ * instances.  A DIFFUSE_AREA rspt_light may name such a primitive (Disk::sample / Cylinder::sample are the follow-up). */
+typedef struct {
+    float object_to_world[16];
+    float world_to_object[16];
+    float height, radius, inner_radius, phi_max;
+    uint32_t reverse_orientation, transform_swaps_handedness;
+    uint32_t medium_inside, medium_outside; /* as in rspt_mesh */
+} rspt_disk; /* 160 B */
+typedef struct {
+    float object_to_world[16];
+    float world_to_object[16];
+    float radius, z_min, z_max, phi_max;
+    uint32_t reverse_orientation, transform_swaps_handedness;
+    uint32_t medium_inside, medium_outside; /* as in rspt_mesh */
+} rspt_cylinder; /* 160 B */
 
 /* ---- participating media (src/core/medium.rs, src/media/{homogeneous,grid}.rs; MakeNamedMedium api.rs:953-1037) ----
  * sigma_a / sigma_s already multiplied by "scale".  The phase function is HenyeyGreenstein { g } (medium.rs:296-331).
@@ -395,6 +425,12 @@ typedef struct {
     const rspt_sphere* spheres;        /* ABI 23: the spheres that rspt_prim records with mesh == RSPT_MESH_SPHERE name */
     uint32_t n_spheres;
     uint32_t pad_spheres;
+    const rspt_disk* disks;            /* ABI 27: the disks that rspt_prim records with mesh == RSPT_MESH_DISK name */
+    uint32_t n_disks;
+    uint32_t pad_disks;
+    const rspt_cylinder* cylinders;    /* ABI 27: ... and the cylinders of mesh == RSPT_MESH_CYLINDER */
+    uint32_t n_cylinders;
+    uint32_t pad_cylinders;
 } rspt_scene_desc;
 
 /* Sampler tables owned by the host.
@@ -722,6 +758,14 @@ enum { RSPT_LIBM_SIN = 0, RSPT_LIBM_COS = 1, RSPT_LIBM_LOG = 2, RSPT_LIBM_LOG2 =
        RSPT_LIBM_TRIANGLE = 8, RSPT_LIBM_BOX = 9, RSPT_LIBM_OFFSET_RAY_ORIGIN = 10, RSPT_LIBM_MICROFACET = 11, RSPT_LIBM_VECTORS = 12, RSPT_LIBM_AREA_LIGHT = 13, RSPT_LIBM_LOBE = 14,
        RSPT_LIBM_SPHERE = 15 };
 int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* out);
+
+/* Stage-level hook (ABI 27).  Replaces: Sphere / Disk / Cylinder ::intersect and ::intersect_p as the traversal and shade kernels call them
+ * (rs_pbrt_amd/csrc/dev_sphere.h, dev_quadric.h).  shape = RSPT_MESH_SPHERE, RSPT_MESH_DISK or RSPT_MESH_CYLINDER; 64 floats per element in
+ * and out, in the layout of RSPT_LIBM_SPHERE: x = the words of one rspt_sphere (42) / rspt_disk (40) / rspt_cylinder (40), then o[3], d[3],
+ * t_max -> out[0] = intersect's result (1 / 0), out[1] = t, p[3], p_error[3], n[3], uv[2], dpdu[3], dpdv[3], dndu[3], dndv[3] (out[2..24]),
+ * the shading frame n, dpdu, dpdv, dndu, dndv (out[25..39]) after transform_surface_interaction, out[43] = intersect_p's result.  With
+ * RSPT_MESH_SPHERE the answer is RSPT_LIBM_SPHERE's.  Any other shape: RSPT_E_INVALID. */
+int rspt_quadric_intersect(uint32_t shape, const float* x, uint64_t n, float* out);
 
 /* Benchmark hook: same as rspt_trace on rays already resident in device memory,
  * repeated `repeat` times; returns average kernel milliseconds per launch. */

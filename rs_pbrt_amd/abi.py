@@ -4,7 +4,7 @@ Every struct here must stay byte-compatible with the header; tests/test_abi.py c
 sizes against the values the library reports."""
 import ctypes as C
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 OK, E_INVALID, E_NODEVICE, E_HIP, E_UNSUPPORTED, E_NOMEM, E_PEER = 0, -1, -2, -3, -4, -5, -6
 
@@ -28,6 +28,8 @@ WRAP_REPEAT, WRAP_BLACK, WRAP_CLAMP = 0, 1, 2
 INSTANCING_REFERENCE, INSTANCING_FIXED = 0, 1
 MESH_INSTANCE = 0xFFFFFFFF
 MESH_SPHERE = 0xFFFFFFFE
+MESH_DISK = 0xFFFFFFFD       # ABI 27
+MESH_CYLINDER = 0xFFFFFFFC   # ABI 27
 LIBM_SPHERE = 15   # rspt_libm: Sphere::intersect + transform_surface_interaction, 64 floats per element (ABI 23)
 NO_MATERIAL = 0xFFFFFFFF
 MISS = 0xFFFFFFFF
@@ -51,6 +53,18 @@ class Sphere(C.Structure):
     _fields_ = [("object_to_world", C.c_float * 16), ("world_to_object", C.c_float * 16), ("radius", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
                 ("theta_min", C.c_float), ("theta_max", C.c_float), ("phi_max", C.c_float), ("reverse_orientation", C.c_uint32),
                 ("transform_swaps_handedness", C.c_uint32), ("medium_inside", C.c_uint32), ("medium_outside", C.c_uint32)]
+
+
+class Disk(C.Structure):   # ABI 27
+    _fields_ = [("object_to_world", C.c_float * 16), ("world_to_object", C.c_float * 16), ("height", C.c_float), ("radius", C.c_float), ("inner_radius", C.c_float),
+                ("phi_max", C.c_float), ("reverse_orientation", C.c_uint32), ("transform_swaps_handedness", C.c_uint32), ("medium_inside", C.c_uint32),
+                ("medium_outside", C.c_uint32)]
+
+
+class Cylinder(C.Structure):   # ABI 27
+    _fields_ = [("object_to_world", C.c_float * 16), ("world_to_object", C.c_float * 16), ("radius", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("phi_max", C.c_float), ("reverse_orientation", C.c_uint32), ("transform_swaps_handedness", C.c_uint32), ("medium_inside", C.c_uint32),
+                ("medium_outside", C.c_uint32)]
 
 
 class Medium(C.Structure):
@@ -113,7 +127,9 @@ class SceneDesc(C.Structure):
                 ("instances", C.c_void_p), ("n_instances", C.c_uint32),
                 ("n_top_nodes", C.c_uint64), ("n_top_prims", C.c_uint64),
                 ("instancing_mode", C.c_uint32), ("n_media", C.c_uint32), ("media", C.c_void_p),
-                ("spheres", C.c_void_p), ("n_spheres", C.c_uint32), ("pad_spheres", C.c_uint32)]
+                ("spheres", C.c_void_p), ("n_spheres", C.c_uint32), ("pad_spheres", C.c_uint32),
+                ("disks", C.c_void_p), ("n_disks", C.c_uint32), ("pad_disks", C.c_uint32),              # ABI 27
+                ("cylinders", C.c_void_p), ("n_cylinders", C.c_uint32), ("pad_cylinders", C.c_uint32)]
 
 
 class SamplerTables(C.Structure):
@@ -174,6 +190,10 @@ MESH_DT = np.dtype([("has_n", "<u4"), ("has_s", "<u4"), ("has_uv", "<u4"), ("fli
 SPHERE_DT = np.dtype([("object_to_world", "<f4", 16), ("world_to_object", "<f4", 16), ("radius", "<f4"), ("z_min", "<f4"), ("z_max", "<f4"),
                       ("theta_min", "<f4"), ("theta_max", "<f4"), ("phi_max", "<f4"), ("reverse_orientation", "<u4"), ("transform_swaps_handedness", "<u4"),
                       ("medium_inside", "<u4"), ("medium_outside", "<u4")])
+DISK_DT = np.dtype([("object_to_world", "<f4", 16), ("world_to_object", "<f4", 16), ("height", "<f4"), ("radius", "<f4"), ("inner_radius", "<f4"), ("phi_max", "<f4"),
+                    ("reverse_orientation", "<u4"), ("transform_swaps_handedness", "<u4"), ("medium_inside", "<u4"), ("medium_outside", "<u4")])
+CYLINDER_DT = np.dtype([("object_to_world", "<f4", 16), ("world_to_object", "<f4", 16), ("radius", "<f4"), ("z_min", "<f4"), ("z_max", "<f4"), ("phi_max", "<f4"),
+                        ("reverse_orientation", "<u4"), ("transform_swaps_handedness", "<u4"), ("medium_inside", "<u4"), ("medium_outside", "<u4")])
 MEDIUM_DT = np.dtype([("kind", "<u4"), ("sigma_a", "<f4", 3), ("sigma_s", "<f4", 3), ("g", "<f4"), ("nx", "<i4"), ("ny", "<i4"), ("nz", "<i4"), ("pad", "<u4"),
                       ("density", "<u8"), ("world_to_medium", "<f4", 16)])
 BXDF_DT = np.dtype([("type", "<u4"), ("fresnel", "<u4"), ("r", "<f4", 3), ("t", "<f4", 3), ("eta_a", "<f4"), ("eta_b", "<f4"),

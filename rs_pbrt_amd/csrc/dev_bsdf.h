@@ -35,11 +35,16 @@ enum : uint32_t {
     SF_L_MAP = 1u << 27,       // ABI 24: a ProjectionLight or GonioPhotometricLight (dev_scene.h map_light_li): a delta light whose intensity a MipMap<Spectrum> modulates
     SF_NO_MAPLIGHT = 1u << 28, // never a scene's need, as SF_TRIS_ONLY: set in every feature set built before those two lights (the sets derived from SF_ALL carry
                                // SF_L_MAP too); a set compiles their arms only with SF_L_MAP and WITHOUT this bit (shade_ml)
+    SF_QUADRIC = 1u << 29,     // ABI 27: disks and cylinders (dev_quadric.h): a hit record with MF_SPHERE builds its Hit from quadric_hit, by its slot's kind
+    SF_NO_QUADRIC = 1u << 30,  // never a scene's need, as SF_TRIS_ONLY: set in every feature set built before those two shapes (the sets derived from SF_ALL carry
+                               // SF_QUADRIC too); a set compiles the quadric arm only with SF_QUADRIC and WITHOUT this bit (shade_quad)
     SF_ALL = 0xffffffffu
 };
 #define RSPT_SF_LOBE(T) (1u << (T))
 // does instantiation F carry the sphere arm?  Only the sphere variants (tu_decl.h SV_*_SPH) do: the triangle sets keep their code and figures
 constexpr bool shade_sph(uint32_t F) { return (F & SF_SPHERE) && !(F & SF_TRIS_ONLY); }
+// ... the quadric arm in its place?  Only the quadric variants (tu_decl.h SV_*_QUAD): the sphere sets keep calling sphere_hit
+constexpr bool shade_quad(uint32_t F) { return shade_sph(F) && (F & SF_QUADRIC) && !(F & SF_NO_QUADRIC); }
 // ... and the projection / goniometric arms?  Only the map-light variants (tu_decl.h SV_*_ML), and with them every caller that passes no F (0xffffffff) keeps its code
 constexpr bool shade_ml(uint32_t F) { return (F & SF_L_MAP) && !(F & SF_NO_MAPLIGHT); }
 

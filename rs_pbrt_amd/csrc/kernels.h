@@ -11,7 +11,7 @@
 // workgroup and queue (K7, in k_shade).
 #pragma once
 #include "dev_texture.h"
-#include "dev_sphere.h"
+#include "dev_quadric.h"
 #include "dev_lens.h"
 #include "pixel_sampler.h"
 
@@ -45,6 +45,26 @@ RDEV void sphere_texhit(const SphereHit& sh, TexHit* h) {
     h->p = sh.p; h->n = sh.n; h->uv = f2{sh.u, sh.v};
     h->dpdu = sh.dpdu; h->dpdv = sh.dpdv;
     h->sh_n = sh.sn; h->sh_dpdu = sh.sdpdu; h->sh_dpdv = sh.sdpdv; h->sh_dndu = sh.sdndu; h->sh_dndv = sh.sdndv;
+}
+// ---- disks and cylinders (ABI 27; the quadric variants only: dev_bsdf.h shade_quad, k_texture_quad, k_ao_spawn_quad) ----
+// The same recomputation for a scene that holds a disk or a cylinder: the slot behind the record is a QuadricDev whose kind picks sphere_hit,
+// disk_hit or cylinder_hit, again on the path's world ray with the ray's OWN t_max.  Cylinder: sphere_fill's argument word for word
+// (cylinder_core picks its root from the quadratic and the z / phi clipping alone; t_max only rejects).  Disk: disk_core has ONE candidate
+// t = (height - o.z) / d.z, and t_max only ever rejects it (t >= t_max); the traversal accepted it under a t_max no larger than the ray's own,
+// so t < t_max holds again, the same branches are taken and the same p and phi come out.
+RDEV const QuadricDev& quadric_of(const SceneDev& sc, const TriRec& t) {
+    return reinterpret_cast<const QuadricDev*>(sc.tris + 3 * (size_t)sc.n_prims)[__float_as_uint(t.p0.x)];   // (t0.x = slot index, dev_quadric.h)
+}
+RDEVN void quadric_fill(const SceneDev& sc, const TriRec& t, f3 o, f3 d, float t_max, Hit* h, f3* wo, SphereHit* out = nullptr) {
+    const QuadricDev& q = quadric_of(sc, t);
+    SphereHit sh;
+    quadric_hit(q, o, d, t_max, &sh);
+    h->p = sh.p; h->p_err = sh.p_error; h->n = sh.n;
+    h->sh_n = sh.sn; h->sh_dpdu = sh.sdpdu;
+    h->material = t.material; h->area_light = t.area_light;
+    // wo = -(object ray).d (disk.rs:149, cylinder.rs:232), transformed back and normalised; the two matrices lead every kind's record
+    if (wo) *wo = normalize(xf_vector(q.s.object_to_world, -xf_vector(q.s.world_to_object, d)));
+    if (out) *out = sh;
 }
 
 // ---- per-path state, SoA by path slot ------------------------------------------------------
@@ -727,7 +747,10 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
             tri_fill<(F & SF_VERTEX) != 0>(sc, prim, tri, hc.y, hc.z, hc.w, &h);
         f3 wo = -ray_d;  // SurfaceInteraction.wo, not normalised (triangle.rs:334)
         if constexpr (shade_sph(F))
-            if (tri.flags & MF_SPHERE) sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &h, &wo);   // (the ray's own t_max: see sphere_fill)
+            if (tri.flags & MF_SPHERE) {
+                if constexpr (shade_quad(F)) quadric_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &h, &wo);   // (a disk, a cylinder or a sphere, by the slot's kind)
+                else sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &h, &wo);   // (the ray's own t_max: see sphere_fill)
+            }
         if ((F & SF_INST) && pb.hit_inst) {  // the hit lies inside an object instance: TransformedPrimitive::intersect (primitive.rs:216-253)
             const uint32_t hi = pb.hit_inst[p];
             const bool moving = (F & SF_ANIM) && hi && sc.inst[hi - 1u].anim != RSPT_MISS;   // (rare: the interpolated Transform of the path's time, as the traversal used it)
@@ -1026,7 +1049,8 @@ RDEVN void texture_hit_call(const SceneDev& sc, const TexTables& tt, TexHit& h, 
 // index: the same slot for the path integrator, slot / H for directlighting's node slots); tix = index of the ray's time (moving instances); with_diff: the ray is the camera
 // ray itself (bounce rays and rays re-spawned behind a null material carry no differentials)
 // SPH: the scene has spheres (k_texture_sph): a sphere record's TexHit comes from sphere_hit on the path's ray (sphere_fill)
-template <bool SPH = false>
+// QUAD (with SPH): the scene has a disk or a cylinder (k_texture_quad): quadric_fill in its place
+template <bool SPH = false, bool QUAD = false>
 RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev& rd, const PathBuf& pb, uint32_t p, uint32_t smp, uint32_t tix, bool with_diff, const f3* lens) {
     const float4 hc = pb.hit_cont[p];
     const uint32_t prim = __float_as_uint(hc.x);
@@ -1041,7 +1065,8 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
             const float4 r0 = rp[0], r1 = rp[1];
             Hit hh;
             SphereHit sh;
-            sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, f3{r0.w, r1.x, r1.y}, r1.z, &hh, nullptr, &sh);
+            if constexpr (QUAD) quadric_fill(sc, tri, f3{r0.x, r0.y, r0.z}, f3{r0.w, r1.x, r1.y}, r1.z, &hh, nullptr, &sh);
+            else sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, f3{r0.w, r1.x, r1.y}, r1.z, &hh, nullptr, &sh);
             sphere_texhit(sh, &h);
         } else
             tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
@@ -1089,14 +1114,14 @@ RDEV void texture_slot(const SceneDev& sc, const TexTables& tt, const RenderDev&
     }
     texture_hit(sc, tt, h, s, tri.material, pb.tex + p, pb.tex_stride);
 }
-template <bool SPH = false>
+template <bool SPH = false, bool QUAD = false>
 RDEVN void texture_path(const SceneDev& sc, const TexTables& tt, const RenderDev& rd, const PathBuf& pb, uint32_t p, const f3* lens) {
     const uint32_t st = pb.state[p];
     if (!(st & ST_ALIVE)) return;
     const uint32_t prim = __float_as_uint(pb.hit_cont[p].x);
     const uint32_t bounces = (st >> ST_BOUNCE_SHIFT) & 0xffu;
     if (prim == RSPT_MISS || bounces >= rd.max_depth) return;
-    texture_slot<SPH>(sc, tt, rd, pb, p, p, p, bounces == 0 && !(st & ST_NO_DIFF) /* the camera ray itself (a null-material pass-through re-spawns without differentials) */, lens);
+    texture_slot<SPH, QUAD>(sc, tt, rd, pb, p, p, p, bounces == 0 && !(st & ST_NO_DIFF) /* the camera ray itself (a null-material pass-through re-spawns without differentials) */, lens);
 }
 
 // ---- K7b: bin the active queue by what the shade stage will do with each path -------------------------------------------
@@ -1135,6 +1160,15 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) RSPT_TEX_OCC void k_texture_sph(SceneDe
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const uint32_t p = q_sorted ? q_sorted[i] : q_active[i];
         if (p != RSPT_BIN_INVALID) [[clang::always_inline]] texture_path<true>(sc, tt, rd, pb, p, nullptr);
+    }
+}
+// ... and for scenes with a disk or a cylinder (ABI 27); k_texture_sph keeps its code
+RSPT_PLAIN_KERNEL __launch_bounds__(256) RSPT_TEX_OCC void k_texture_quad(SceneDev sc, TexTables tt, RenderDev rd, PathBuf pb, const uint32_t* __restrict__ q_active,
+                                                      const uint32_t* __restrict__ count_in, const uint32_t* __restrict__ q_sorted, const BinInfo* __restrict__ bi) {
+    const uint32_t n = q_sorted ? bi->total : *count_in;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t p = q_sorted ? q_sorted[i] : q_active[i];
+        if (p != RSPT_BIN_INVALID) [[clang::always_inline]] texture_path<true, true>(sc, tt, rd, pb, p, nullptr);
     }
 }
 RDEV uint32_t bin_key(const SceneDev& sc, const PathBuf& pb, uint32_t max_depth, uint32_t p) {
@@ -1363,7 +1397,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_move_flush(PathBuf pb, const uin
 // term dot(wi, n) / (pdf * n) that stage 2 adds when the ray is unoccluded.
 #define RSPT_AO_SKIP 0xffffffffu  // id of a ray that is not traced (pdf == 0)
 // ANIM: the scene has moving instances (their Transform at the camera sample's time, inst_at); SPH: the scene has spheres (sphere_fill)
-template <bool ANIM, bool SPH>
+template <bool ANIM, bool SPH, bool QUAD = false>   // QUAD (with SPH): the scene has a disk or a cylinder (quadric_fill)
 __device__ __forceinline__ void ao_spawn(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
                                                   uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -1381,7 +1415,8 @@ __device__ __forceinline__ void ao_spawn(SceneDev sc, RenderDev rd, Batch bt, Pa
     Hit hp;    // p_error for spawn_ray
     if (SPH && (tri.flags & MF_SPHERE)) {
         SphereHit sh;
-        sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &hp, nullptr, &sh);
+        if constexpr (QUAD) quadric_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &hp, nullptr, &sh);
+        else sphere_fill(sc, tri, f3{r0.x, r0.y, r0.z}, ray_d, r1.z, &hp, nullptr, &sh);
         sphere_texhit(sh, &h);
     } else {
         tri_fill_tex(sc, prim, tri, hc.y, hc.z, hc.w, &h);
@@ -1436,6 +1471,10 @@ __global__ __launch_bounds__(256) void k_ao_spawn(SceneDev sc, RenderDev rd, Bat
 RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_ao_spawn_sph(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
                                                   uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {   // scenes with spheres (never with instances)
     ao_spawn<false, true>(sc, rd, bt, pb, pix_list, n_samples, cos_sample, q_any, cnt);
+}
+RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_ao_spawn_quad(SceneDev sc, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list,
+                                                   uint32_t n_samples, uint32_t cos_sample, uint32_t* __restrict__ q_any, QueueCounts* cnt) {   // scenes with a disk or a cylinder (ABI 27)
+    ao_spawn<false, true, true>(sc, rd, bt, pb, pix_list, n_samples, cos_sample, q_any, cnt);
 }
 // Stage 2: l += Spectrum::new(term) for the unoccluded rays, in array order (ao.rs:86-91)
 RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_ao_resolve(Batch bt, PathBuf pb, uint32_t n_samples) {

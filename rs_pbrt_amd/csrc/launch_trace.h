@@ -224,6 +224,14 @@ void launch_trace_sph(const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur)
         hipLaunchKernelGGL(kern, dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
                            c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, (uint32_t)RSPT_W4_SPILL, p.refill, p.leaf, s->w4_top, nullptr, xcur, p.chunk);
     };
+    if (s->has_quadrics) {   // ABI 27: a disk or a cylinder in the scene: the kernels whose leaf phase reads the slot's kind (trace_w4.h k_trace_w4quad)
+        if (OUT_MODE == 1 && getenv("RSPT_VERBOSE"))   // (the trace hook only: a render launches this hundreds of times)
+            fprintf(stderr, "rspt: trace instantiation 'k_trace_w4quad<%s, alpha %d>'\n", ANY ? "any" : "closest", !s->has_alpha ? 0 : (s->alpha_simple ? 2 : 1));
+        if (!s->has_alpha) go(k_trace_w4quad<ANY, OUT_MODE, 0>);
+        else if (s->alpha_simple) go(k_trace_w4quad<ANY, OUT_MODE, 2>);
+        else go(k_trace_w4quad<ANY, OUT_MODE, 1>);
+        return;
+    }
     if (!s->has_alpha) go(k_trace_w4<ANY, OUT_MODE, false, 0, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
     else if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, false, 2, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
     else go(k_trace_w4<ANY, OUT_MODE, false, 1, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>);
@@ -270,6 +278,10 @@ const ShadeVariant g_shade_variants[] = {
     // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
     {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
     {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
+    // scenes with a disk or a cylinder (ABI 27, SF_QUADRIC): the two sphere sets with quadric_fill in place of sphere_fill (dev_bsdf.h shade_quad); they serve
+    // that scene's spheres and triangles too.  Only such scenes take them and such scenes take nothing else.  Figures: DESIGN section 5.1b.
+    {SV_GENERIC_QUAD, "generic-quadric", k_shade<SV_GENERIC_QUAD>, k_shade<SV_GENERIC_QUAD>, k_shade<SV_GENERIC_QUAD>, 0, nullptr},
+    {SV_DYNAMIC_QUAD, "dynamic-quadric", k_shade<SV_DYNAMIC_QUAD>, k_shade<SV_DYNAMIC_QUAD>, k_shade<SV_DYNAMIC_QUAD>, 0, nullptr},
     // scenes with a projection or goniometric light (ABI 24, SF_L_MAP; Sobol' and Halton): the generic and the all-features set with the two arms of
     // light_sample_li / light_is_delta (dev_bsdf.h shade_ml).  Only such scenes take them and such scenes take nothing else.  No MOVE form: the
     // schedule was left off for them (unmeasured there), they keep slots for life.
@@ -281,9 +293,10 @@ const ShadeVariant g_shade_variants[] = {
 ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
     const char* force = getenv("RSPT_SHADE_VARIANT");
     if (move_out) *move_out = nullptr;
-    const bool sph = (need & SF_SPHERE) != 0, ml = (need & SF_L_MAP) != 0;
+    const bool sph = (need & SF_SPHERE) != 0, ml = (need & SF_L_MAP) != 0, quad = (need & SF_QUADRIC) != 0;
     for (const ShadeVariant& v : g_shade_variants) {
         if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
+        if (shade_quad(v.features) != quad) continue; // (... and SF_QUADRIC: SF_NO_QUADRIC; a quadric scene's need carries SF_SPHERE too)
         if (shade_ml(v.features) != ml) continue;     // (... and SF_L_MAP: SF_NO_MAPLIGHT)
         if ((need & ~v.features) != 0) continue;
         if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;

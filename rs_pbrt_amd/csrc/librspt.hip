@@ -275,6 +275,11 @@ struct rspt_scene_s {
     bool has_maplights = false;       // ABI 24: a projection or goniometric light (dev_scene.h light_sample_li's two arms); rspt_render serves them under path (Sobol', Halton) and ao
     bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); rspt_render serves them under path / ao (Sobol', Halton)
     bool has_sphere_light = false;    // an emissive sphere: refused by rspt_render and the light-distribution hook (sphere area lights are not on the device)
+    // ABI 27: a disk or a cylinder (dev_quadric.h).  Such a scene also sets has_spheres — its records sit in the sphere slots and it takes every path a sphere scene
+    // takes — and has_quadrics picks the instantiations that read a slot's kind.  quadric_kinds / quadric_light_kinds: "disk", "cylinder" or "disk and cylinder", for the refusals
+    bool has_quadrics = false, has_disks = false, has_cylinders = false;
+    const char* quadric_kinds = "";
+    const char* quadric_light_kinds = nullptr, *quadric_light_what = "";   // which of them emit ("disk", .. / "disk area lights", ..): refused by rspt_render and the light-distribution hook (Disk::sample / Cylinder::sample are not on the device)
     std::map<int, LightDist> light_dists;  // by effective strategy
 };
 
@@ -773,6 +778,8 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     const bool instanced = d->n_instances > 0;
     const uint64_t n_top_prims = instanced ? d->n_top_prims : d->n_prims, n_top_nodes = instanced ? d->n_top_nodes : d->n_nodes;
     if (d->n_spheres && instanced) return fail(RSPT_E_UNSUPPORTED, "spheres together with object instances");   // (ABI 23: a follow-up)
+    if (d->n_disks && instanced) return fail(RSPT_E_UNSUPPORTED, "disks together with object instances");
+    if (d->n_cylinders && instanced) return fail(RSPT_E_UNSUPPORTED, "cylinders together with object instances");
     if (instanced) {  // objects + instances behind the top-level aggregate
         if (!d->instances || !d->objects || d->n_objects == 0) return fail(RSPT_E_INVALID, "instances without objects");
         if (n_top_prims > d->n_prims || n_top_nodes > d->n_nodes || n_top_nodes == 0) return fail(RSPT_E_INVALID, "bad top-level aggregate range");
@@ -803,8 +810,45 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             return fail(RSPT_E_INVALID, "sphere %u: radius must be positive and finite, z / theta / phi finite", i);
         if (sp.medium_inside > d->n_media || sp.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "sphere %u: medium index out of range", i);
     }
+    // ABI 27: disks and cylinders (dev_quadric.h)
+    if (d->n_disks && !d->disks) return fail(RSPT_E_INVALID, "null disks with n_disks > 0");
+    if (d->n_cylinders && !d->cylinders) return fail(RSPT_E_INVALID, "null cylinders with n_cylinders > 0");
+    if ((uint64_t)d->n_spheres + d->n_disks + d->n_cylinders > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "more than 2^31 spheres, disks and cylinders");
+    for (uint32_t i = 0; i < d->n_disks; i++) {
+        const rspt_disk& k = d->disks[i];
+        for (int j = 0; j < 16; j++)
+            if (!std::isfinite(k.object_to_world[j]) || !std::isfinite(k.world_to_object[j])) return fail(RSPT_E_INVALID, "disk %u: non-finite transform", i);
+        if (!std::isfinite(k.height) || !std::isfinite(k.radius) || !std::isfinite(k.inner_radius) || !std::isfinite(k.phi_max)) return fail(RSPT_E_INVALID, "disk %u: non-finite parameter", i);
+        if (!(k.radius > 0.0f)) return fail(RSPT_E_INVALID, "disk %u: radius must be positive", i);
+        if (k.radius == k.inner_radius) return fail(RSPT_E_INVALID, "disk %u: radius equals inner_radius (v divides by their difference)", i);
+        if (!(k.phi_max > 0.0f && k.phi_max <= 2.0f * RSPT_PI)) return fail(RSPT_E_INVALID, "disk %u: phi_max outside (0, 2 pi]", i);
+        if (k.medium_inside > d->n_media || k.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "disk %u: medium index out of range", i);
+    }
+    for (uint32_t i = 0; i < d->n_cylinders; i++) {
+        const rspt_cylinder& k = d->cylinders[i];
+        for (int j = 0; j < 16; j++)
+            if (!std::isfinite(k.object_to_world[j]) || !std::isfinite(k.world_to_object[j])) return fail(RSPT_E_INVALID, "cylinder %u: non-finite transform", i);
+        if (!std::isfinite(k.radius) || !std::isfinite(k.z_min) || !std::isfinite(k.z_max) || !std::isfinite(k.phi_max)) return fail(RSPT_E_INVALID, "cylinder %u: non-finite parameter", i);
+        if (!(k.radius > 0.0f)) return fail(RSPT_E_INVALID, "cylinder %u: radius must be positive", i);
+        if (k.z_min == k.z_max) return fail(RSPT_E_INVALID, "cylinder %u: z_min equals z_max (v divides by their difference)", i);
+        if (!(k.phi_max > 0.0f && k.phi_max <= 2.0f * RSPT_PI)) return fail(RSPT_E_INVALID, "cylinder %u: phi_max outside (0, 2 pi]", i);
+        if (k.medium_inside > d->n_media || k.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "cylinder %u: medium index out of range", i);
+    }
+    bool disk_light = false, cylinder_light = false;
     for (uint64_t i = 0; i < d->n_prims; i++) {
         const rspt_prim& p = d->prims[i];
+        if (p.mesh == RSPT_MESH_DISK || p.mesh == RSPT_MESH_CYLINDER) {
+            const bool dk = p.mesh == RSPT_MESH_DISK;
+            const char* kn = dk ? "disk" : "cylinder";
+            if (p.v[0] >= (dk ? d->n_disks : d->n_cylinders)) return fail(RSPT_E_INVALID, "prim %llu: %s index out of range", (unsigned long long)i, kn);
+            if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: %s's material index out of range", (unsigned long long)i, kn);
+            if (p.area_light < -1 || p.area_light >= (int64_t)d->n_lights) return fail(RSPT_E_INVALID, "prim %llu: %s's light index out of range", (unsigned long long)i, kn);
+            if (p.area_light >= 0 && (d->lights[p.area_light].kind != RSPT_LIGHT_DIFFUSE_AREA || d->lights[p.area_light].prim != i))
+                return fail(RSPT_E_INVALID, "prim %llu: %s's area light %d is not a DIFFUSE_AREA light on this primitive", (unsigned long long)i, kn, p.area_light);
+            if (p.area_light >= 0) (dk ? disk_light : cylinder_light) = true;
+            has_null |= p.material == 0xffffffffu;
+            continue;
+        }
         if (p.mesh == RSPT_MESH_SPHERE) {
             if (p.v[0] >= d->n_spheres) return fail(RSPT_E_INVALID, "prim %llu: sphere index out of range", (unsigned long long)i);
             if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: material index out of range", (unsigned long long)i);
@@ -859,6 +903,9 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             return fail(RSPT_E_INVALID, "light %u: prim out of range", i);
         if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && d->prims[d->lights[i].prim].mesh == RSPT_MESH_SPHERE && d->prims[d->lights[i].prim].area_light != (int32_t)i)
             return fail(RSPT_E_INVALID, "light %u: its sphere primitive names another light", i);
+        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->prims[d->lights[i].prim].mesh == RSPT_MESH_DISK || d->prims[d->lights[i].prim].mesh == RSPT_MESH_CYLINDER) &&
+            d->prims[d->lights[i].prim].area_light != (int32_t)i)
+            return fail(RSPT_E_INVALID, "light %u: its %s primitive names another light", i, d->prims[d->lights[i].prim].mesh == RSPT_MESH_DISK ? "disk" : "cylinder");
         if (d->lights[i].kind == RSPT_LIGHT_INFINITE && d->lights[i].prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u: envmap index out of range", i);
         if (d->lights[i].kind == RSPT_LIGHT_PROJECTION || d->lights[i].kind == RSPT_LIGHT_GONIOMETRIC) {   // ABI 24
             const rspt_light& l = d->lights[i];
@@ -1048,6 +1095,15 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     const rspt_mesh* meshes_d = nullptr;
     const float* P_d = nullptr;
     if ((rc = upload(s, d->nodes, d->n_nodes, &nodes_d))) return bail(rc);
+    const bool quadrics = d->n_disks || d->n_cylinders;
+    if (quadrics) {   // ABI 27: on the device a disk or cylinder primitive is a sphere primitive whose index names its slot behind the triangle records (dev_quadric.h: spheres, disks, cylinders)
+        std::vector<rspt_prim> pv(d->prims, d->prims + d->n_prims);
+        for (rspt_prim& p : pv) {
+            if (p.mesh == RSPT_MESH_DISK) { p.mesh = RSPT_MESH_SPHERE; p.v[0] += d->n_spheres; }
+            else if (p.mesh == RSPT_MESH_CYLINDER) { p.mesh = RSPT_MESH_SPHERE; p.v[0] += d->n_spheres + d->n_disks; }
+        }
+        if ((rc = upload(s, pv.data(), pv.size(), &s->dev.prims))) return bail(rc);
+    } else
     if ((rc = upload(s, d->prims, d->n_prims, &s->dev.prims))) return bail(rc);
     if ((rc = upload(s, d->meshes, d->n_meshes, &meshes_d))) return bail(rc);
     s->dev.meshes = meshes_d;
@@ -1079,7 +1135,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             std::vector<float> nuv((size_t)d->n_prims * 20, 0.0f);
             for (uint64_t i = 0; i < d->n_prims; i++) {
                 const rspt_prim& pr = d->prims[i];
-                if (pr.mesh == RSPT_MESH_INSTANCE || pr.mesh == RSPT_MESH_SPHERE) continue;
+                if (pr.mesh == RSPT_MESH_INSTANCE || pr.mesh == RSPT_MESH_SPHERE || pr.mesh == RSPT_MESH_DISK || pr.mesh == RSPT_MESH_CYLINDER) continue;
                 const rspt_mesh& me = d->meshes[pr.mesh];
                 float* q = nuv.data() + 20 * i;
                 for (int k = 0; k < 3; k++) {
@@ -1326,7 +1382,7 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
         bool any_alpha = false;
         for (uint32_t i = 0; i < d->n_meshes; i++) any_alpha = any_alpha || d->meshes[i].alpha_tex || d->meshes[i].shadow_alpha_tex;
         // (not for scenes with spheres either: k_trace_w4q walks triangle leaves only, and launch_trace_sph never takes it)
-        if (s->w4_ok && !recs.empty() && !instanced && !any_alpha && d->n_spheres == 0 && env_size("RSPT_W4Q_BUILD", 1) != 0) {
+        if (s->w4_ok && !recs.empty() && !instanced && !any_alpha && d->n_spheres == 0 && !quadrics && env_size("RSPT_W4Q_BUILD", 1) != 0) {
             std::vector<Quad4Node> q(recs.size());
             bool ok = true;
             for (size_t i = 0; i < recs.size() && ok; i++) {
@@ -1380,7 +1436,8 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     if (d->n_prims) {
         float4* tris = nullptr;
         // a scene with spheres keeps them behind the triangle records (dev_sphere.h SphereDev, RSPT_SPHERE_F4 float4 each)
-        hipError_t e = hipMalloc((void**)&tris, (d->n_prims * 3 + (uint64_t)d->n_spheres * RSPT_SPHERE_F4) * sizeof(float4));
+        const uint64_t n_slots = (uint64_t)d->n_spheres + d->n_disks + d->n_cylinders;   // (disks and cylinders take sphere slots, ABI 27)
+        hipError_t e = hipMalloc((void**)&tris, (d->n_prims * 3 + n_slots * RSPT_SPHERE_F4) * sizeof(float4));
         if (e != hipSuccess) return bail(fail(RSPT_E_NOMEM, "triangle records: %s", hipGetErrorString(e)));
         s->allocs.push_back(tris);
         const uint32_t* inst_cont_d = nullptr;
@@ -1438,6 +1495,23 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
             s->shade_features |= SF_SPHERE;
             for (uint64_t i = 0; i < d->n_prims; i++)
                 if (d->prims[i].mesh == RSPT_MESH_SPHERE && d->prims[i].area_light != -1) s->has_sphere_light = true;
+        }
+        if (quadrics) {   // ABI 27: every slot again with its kind — the spheres (kind 0, as written above), then the disks, then the cylinders
+            std::vector<QuadricDev> q(n_slots);
+            memset(q.data(), 0, q.size() * sizeof(QuadricDev));
+            for (uint32_t k = 0; k < d->n_spheres; k++) { q[k].s = d->spheres[k]; q[k].kind = QK_SPHERE; }
+            for (uint32_t k = 0; k < d->n_disks; k++) { q[d->n_spheres + k].d = d->disks[k]; q[d->n_spheres + k].kind = QK_DISK; }
+            for (uint32_t k = 0; k < d->n_cylinders; k++) { q[d->n_spheres + d->n_disks + k].c = d->cylinders[k]; q[d->n_spheres + d->n_disks + k].kind = QK_CYLINDER; }
+            e = hipMemcpy(tris + 3 * d->n_prims, q.data(), q.size() * sizeof(QuadricDev), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "disk / cylinder records: %s", hipGetErrorString(e)));
+            s->has_spheres = s->has_quadrics = true;
+            s->has_disks = d->n_disks != 0; s->has_cylinders = d->n_cylinders != 0;
+            s->quadric_kinds = s->has_disks && s->has_cylinders ? "disk and cylinder" : (s->has_disks ? "disk" : "cylinder");
+            if (disk_light || cylinder_light) {
+                s->quadric_light_kinds = disk_light && cylinder_light ? "disk and cylinder" : (disk_light ? "disk" : "cylinder");
+                s->quadric_light_what = disk_light && cylinder_light ? "disk area lights and cylinder area lights" : (disk_light ? "disk area lights" : "cylinder area lights");
+            }
+            s->shade_features |= SF_SPHERE | SF_QUADRIC;
         }
         s->dev.tris = tris;
         if (s->w4_ok && s->w4 && !instanced && (!s->has_alpha || s->alpha_simple) && env_size("RSPT_SERIAL_W4", 1) != 0) {   // the per-lane kernels' traversal (trace_serial.h)
@@ -1804,8 +1878,53 @@ __global__ void k_leaf_sphere(const float* __restrict__ x, uint64_t n, float* __
     float t = 0.0f;
     r[43] = sphere_test(sp, o, d, q[6], &t) ? 1.0f : 0.0f;
 }
+// rspt_quadric_intersect (ABI 27): one rspt_sphere / rspt_disk / rspt_cylinder + o, d, t_max -> quadric_hit and quadric_test (dev_quadric.h) as the quadric
+// instantiations call them; 64 floats in and out, in k_leaf_sphere's layout
+__global__ void k_leaf_quadric(uint32_t kind, uint32_t n_words, const float* __restrict__ x, uint64_t n, float* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    QuadricDev qd;
+    uint32_t* sw = reinterpret_cast<uint32_t*>(&qd);
+    for (uint32_t k = 0; k < 44u; k++) sw[k] = k < n_words ? __float_as_uint(x[64 * i + k]) : 0u;
+    qd.kind = kind;
+    const float* q = x + 64 * i + n_words;
+    const f3 o{q[0], q[1], q[2]}, d{q[3], q[4], q[5]};
+    float* r = out + 64 * i;
+    for (int k = 0; k < 64; k++) r[k] = 0.0f;
+    SphereHit h;
+    if (quadric_hit(qd, o, d, q[6], &h)) {
+        const f3 v[13] = {h.p, h.p_error, h.n, f3{h.u, h.v, 0.0f}, h.dpdu, h.dpdv, h.dndu, h.dndv, h.sn, h.sdpdu, h.sdpdv, h.sdndu, h.sdndv};
+        r[0] = 1.0f; r[1] = h.t;
+        int k = 2;
+        for (int j = 0; j < 13; j++) {
+            r[k++] = v[j].x; r[k++] = v[j].y;
+            if (j != 3) r[k++] = v[j].z;
+        }
+    }
+    float t = 0.0f;
+    r[43] = quadric_test(qd, o, d, q[6], &t) ? 1.0f : 0.0f;
+}
 }  // namespace
 extern "C" {
+int rspt_quadric_intersect(uint32_t shape, const float* x, uint64_t n, float* out) {
+    if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
+    if (shape != RSPT_MESH_SPHERE && shape != RSPT_MESH_DISK && shape != RSPT_MESH_CYLINDER) return fail(RSPT_E_INVALID, "bad shape %#x (RSPT_MESH_SPHERE, RSPT_MESH_DISK, RSPT_MESH_CYLINDER)", shape);
+    if (n == 0) return RSPT_OK;
+    if (!x || !out || n > (1ull << 25)) return fail(RSPT_E_INVALID, "null argument or more than 2^25 elements");
+    HIP_TRY(hipSetDevice(g.device));
+    float *xd = nullptr, *od = nullptr;
+    struct Guard { float **a, **b; ~Guard() { for (float** p : {a, b}) if (*p) (void)hipFree(*p); } } guard{&xd, &od};
+    int rc;
+    if ((rc = dev_alloc(&xd, n * 64)) || (rc = dev_alloc(&od, n * 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(xd, x, n * 64 * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    const uint32_t kind = shape == RSPT_MESH_SPHERE ? QK_SPHERE : (shape == RSPT_MESH_DISK ? QK_DISK : QK_CYLINDER);
+    hipLaunchKernelGGL(k_leaf_quadric, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, kind, kind == QK_SPHERE ? 42u : 40u, xd, n, od);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, od, n * 64 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RSPT_OK;
+}
+
 int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* out) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (n == 0) return RSPT_OK;
@@ -1832,6 +1951,7 @@ int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3],
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
     // (a scene whose spheres are no lights needs no sphere code here: the spatial voxels take the world bound from the BVH root, which holds the spheres)
+    if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: the light distributions are not built for %s yet", s->quadric_light_kinds, s->quadric_light_what);
     if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
     // (a scene with projection / goniometric lights: get_light_dist launches the kernels that carry their arms, and refuses the on-demand table)
     const uint32_t nl = s->dev.n_lights;
@@ -1885,6 +2005,7 @@ int rspt_trace_device(rspt_scene_t s, const void* rays_dev, uint64_t n, void* ou
     if (!s || (n && (!rays_dev || !out_dev))) return fail(RSPT_E_INVALID, "null argument");
     if (n > 0xfffffff0ull) return fail(RSPT_E_UNSUPPORTED, "more than 2^32 rays per call");
     if (repeat < 1) repeat = 1;
+    if (s->has_quadrics && !s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "%s scene with more four-box records than a reference holds", s->quadric_kinds);
     if (s->has_spheres && !s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "sphere scene with more four-box records than a reference holds");
     HIP_TRY(hipSetDevice(g.device));
     if (!g.totals) { int rc = dev_alloc(&g.totals, 8); if (rc) return rc; }

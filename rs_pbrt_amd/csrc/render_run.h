@@ -106,6 +106,23 @@ int RenderRun::validate() {
     // (Sobol' / Halton).  Everything else that holds a sphere is refused, so the caller keeps its CPU loop: sphere area lights (their
     // sample_with_ref_point / pdf_with_ref_point and power are not on the device), the directlighting / whitted / volpath forms and the pixel
     // samplers (their per-lane walks, trace_serial.h, have no sphere test), and a sphere scene whose records outgrow the four-box kernel.
+    // ABI 27: disks and cylinders are served exactly where spheres are; their refusals name them (a scene without one keeps the sphere wording below)
+    if (s->has_quadrics) {
+        static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
+        const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
+        const char* q = s->quadric_kinds;
+        if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: %s are not served on the device yet (%s)", s->quadric_light_kinds, s->quadric_light_what, iname);
+        if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are not served on the device yet (%s)", q, iname);
+        if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+            return fail(RSPT_E_UNSUPPORTED, "scene with a %s under the %s integrator: these shapes are served by path and ao only", q, iname);
+        if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+            return fail(RSPT_E_UNSUPPORTED, "scene with a %s under the %s sampler: these shapes are served with the sobol and halton samplers only", q,
+                        d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                        d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+        if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "%s scene with more four-box records than a reference holds", q);
+        if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with a %s: the quadric traversal keeps no node counters", q);
+        if (s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light next to a %s: that pair has no shade instantiation yet", s->maplight_kinds, q);
+    } else
     if (s->has_spheres) {
         static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
         const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
@@ -290,6 +307,7 @@ int RenderRun::constants() {
 
     if ((rc = get_light_dist(s, d->light_strategy, &ld, &ld_lazy))) return rc;
     // (k_ld_mark finds a hit's voxel from its barycentrics: a sphere scene takes the eager table or nothing)
+    if (ld_lazy && s->has_quadrics) return fail(RSPT_E_UNSUPPORTED, "scene with a %s whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)", s->quadric_kinds);
     if (ld_lazy && s->has_spheres) return fail(RSPT_E_UNSUPPORTED, "scene with spheres whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)");
     if (volpath && s->dev.n_grid_media && !pixel_sampler)
         return fail(RSPT_E_UNSUPPORTED, "volpath with a grid-density medium under the Sobol' / Halton sampler: every tracking step draws sampler dimensions (the reference panics past "
@@ -413,6 +431,7 @@ int RenderRun::size_batches() {
     // (their ray times are kept by original slot) and not under the pixel samplers / the other integrators, which keep slots for life.  RSPT_MOVE=0: slots, as before.
     shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k);
     if (!shade_k) return fail(RSPT_E_UNSUPPORTED, s->has_maplights ? "RSPT_SHADE_VARIANT names no instantiation with the projection / goniometric arms (generic-maplight, all-maplight)"
+                                                                  : s->has_quadrics ? "RSPT_SHADE_VARIANT names no instantiation with the disk / cylinder arm (generic-quadric, dynamic-quadric)"
                                                                   : "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
     move = !volpath && !direct && !ao && !pixel_sampler && !s->has_animated && shade_move_k != nullptr && env_size("RSPT_MOVE", 1) != 0;
     // the first iteration that runs the MOVE kernel.  Iteration 0 reads a dense pixel-major queue whatever the schedule and its stores are dense too (every slot is

@@ -332,7 +332,7 @@ int RenderRun::batch_ao(const Batch& bt, uint32_t& it) {  // AOIntegrator::li: c
     launch_trace<false, 0>(tgrid, s, closest_call(g.pb, g.q[0][1], &g.cnt[0].closest, &g.cnt[0].cursor_closest, counters));
     ev_close(0, 0);
     HIP_TRY(hipEventRecord(e1, g.stream));
-    hipLaunchKernelGGL(s->has_spheres ? k_ao_spawn_sph : (s->has_animated ? k_ao_spawn<true> : k_ao_spawn<false>), dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, g.pix_list, ao_n, d->ao_cos_sample, g.q[0][2], &g.cnt[1]);
+    hipLaunchKernelGGL(s->has_quadrics ? k_ao_spawn_quad : s->has_spheres ? k_ao_spawn_sph : (s->has_animated ? k_ao_spawn<true> : k_ao_spawn<false>), dim3((bt.n + 255) / 256), dim3(256), 0, g.stream, s->dev, rd, bt, g.pb, g.pix_list, ao_n, d->ao_cos_sample, g.q[0][2], &g.cnt[1]);
     HIP_TRY(hipEventRecord(e2, g.stream));
     ev_open(1, 0);
     s->dev.time_div = ao_n;   // shadow ray k of camera sample i sits in slot i * n + k: its Ray.time is the sample's (moving instances)
@@ -409,7 +409,7 @@ int RenderRun::batch_path(const Batch& bt, uint32_t& it) {  // PathIntegrator::l
         }
         if (s->has_textures) {
             const bool tex_sorted = bins_now && env_size("RSPT_TEXTURE_SORTED", 1) != 0;
-            hipLaunchKernelGGL(s->has_spheres ? k_texture_sph : k_texture, dim3(sgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, P, g.q[par][0], &g.cnt[it].active,
+            hipLaunchKernelGGL(s->has_quadrics ? k_texture_quad : s->has_spheres ? k_texture_sph : k_texture, dim3(sgrid), dim3(256), 0, g.stream, s->dev, s->tex, rd, P, g.q[par][0], &g.cnt[it].active,
                                tex_sorted ? g.q_sorted : (const uint32_t*)nullptr, tex_sorted ? &g.bin_info[it] : (const BinInfo*)nullptr);
         }
         hipLaunchKernelGGL((move && it >= move_first) ? shade_move_k : shade_k, dim3(hinted_grid(queue_hint, sgrid, 256)), dim3(256), sob_nd * sob_bits * sizeof(uint32_t), g.stream, s->dev, ld, rd, P, g.q[par][0], &g.cnt[it], &g.cnt[it + 1], g.q[par ^ 1][0],

@@ -26,6 +26,9 @@ constexpr uint32_t SV_DYNAMIC = SF_ALL & ~SF_ANIM;                              
 constexpr uint32_t SV_GENERIC_SPH = SV_GENERIC & ~SF_TRIS_ONLY, SV_DYNAMIC_SPH = SV_DYNAMIC & ~SF_TRIS_ONLY;
 // scenes with a projection or goniometric light (ABI 24; dev_bsdf.h shade_ml): the generic set and the all-features set with those two arms; every set above
 // keeps SF_NO_MAPLIGHT (or never had SF_L_MAP) and so its code
+// scenes with a disk or a cylinder (ABI 27; dev_bsdf.h shade_quad): the two sphere sets with the quadric arm in place of the sphere arm; every set above keeps
+// SF_NO_QUADRIC and so its code
+constexpr uint32_t SV_GENERIC_QUAD = SV_GENERIC_SPH & ~SF_NO_QUADRIC, SV_DYNAMIC_QUAD = SV_DYNAMIC_SPH & ~SF_NO_QUADRIC;
 constexpr uint32_t SV_GENERIC_ML = SV_GENERIC & ~SF_NO_MAPLIGHT, SV_ALL_ML = SF_ALL & ~SF_NO_MAPLIGHT;
 
 #define RSPT_TU_TS(I, A, M) \
@@ -53,6 +56,10 @@ constexpr uint32_t SV_GENERIC_ML = SV_GENERIC & ~SF_NO_MAPLIGHT, SV_ALL_ML = SF_
     RSPT_TU_X template __global__ void k_trace_w4<ANY, OM, false, A, false, RSPT_PW_BLOCK, RSPT_W4_TOP, true>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, \
                                                                   uint32_t*, const rspt_ray*, const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, \
                                                                   uint32_t*, uint32_t*, uint32_t);   /* scenes with spheres: the trace hook (OM 1), the render's queues (OM 0) */
+#define RSPT_TU_W4QUAD(ANY, OM, A) \
+    RSPT_TU_X template __global__ void k_trace_w4quad<ANY, OM, A>(SceneDev, TexTables, const Wide4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, \
+                                                                  const rspt_ray*, float4*, float4*, uint32_t*, rspt_hit*, uint32_t*, uint32_t*, uint2*, uint32_t, int, int, uint32_t, uint32_t*, uint32_t*, \
+                                                                  uint32_t);   /* scenes with a disk or a cylinder (ABI 27): the trace hook (OM 1), the render's queues (OM 0) */
 #define RSPT_TU_W4_4(ANY, OM) RSPT_TU_W4(ANY, OM, false, 0) RSPT_TU_W4(ANY, OM, false, 1) RSPT_TU_W4(ANY, OM, true, 0) RSPT_TU_W4(ANY, OM, true, 1)
 #define RSPT_TU_W4_S(ANY, OM) RSPT_TU_W4(ANY, OM, false, 2) RSPT_TU_W4(ANY, OM, true, 2)   /* alpha masks evaluated in line (alpha_simple) */
 #define RSPT_TU_REF(ANY, OM, C, I, A) \
@@ -155,6 +162,12 @@ RSPT_TU_SHADE(SV_DYNAMIC) RSPT_TU_SHADE(SF_ALL)
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_S)
 RSPT_TU_SHADE(SV_GENERIC_SPH) RSPT_TU_SHADE(SV_DYNAMIC_SPH)   /* scenes with spheres; no MOVE form: they keep slots for life */
 #endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_Q)
+RSPT_TU_SHADE(SV_GENERIC_QUAD)   /* scenes with a disk or a cylinder; no MOVE form, as for spheres */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_QD)
+RSPT_TU_SHADE(SV_DYNAMIC_QUAD)
+#endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_L)
 RSPT_TU_SHADE(SV_GENERIC_ML) RSPT_TU_SHADE(SV_ALL_ML)   /* scenes with projection / goniometric lights; no MOVE form */
 #endif
@@ -206,6 +219,12 @@ RSPT_TU_W4SPH(false, 0) RSPT_TU_W4SPH(false, 1) RSPT_TU_W4SPH(false, 2) RSPT_TU_
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4SPH0)
 RSPT_TU_W4SPHO(false, 0, 0) RSPT_TU_W4SPHO(false, 0, 1) RSPT_TU_W4SPHO(false, 0, 2) RSPT_TU_W4SPHO(true, 0, 0) RSPT_TU_W4SPHO(true, 0, 1) RSPT_TU_W4SPHO(true, 0, 2)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4QUAD)
+RSPT_TU_W4QUAD(false, 1, 0) RSPT_TU_W4QUAD(false, 1, 1) RSPT_TU_W4QUAD(false, 1, 2) RSPT_TU_W4QUAD(true, 1, 0) RSPT_TU_W4QUAD(true, 1, 1) RSPT_TU_W4QUAD(true, 1, 2)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4QUAD0)
+RSPT_TU_W4QUAD(false, 0, 0) RSPT_TU_W4QUAD(false, 0, 1) RSPT_TU_W4QUAD(false, 0, 2) RSPT_TU_W4QUAD(true, 0, 0) RSPT_TU_W4QUAD(true, 0, 1) RSPT_TU_W4QUAD(true, 0, 2)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4A)
 RSPT_TU_W4A(false, 0) RSPT_TU_W4A(false, 1) RSPT_TU_W4A(true, 0) RSPT_TU_W4A(true, 1)

@@ -17,7 +17,7 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
            "rspt_dev_upload", "rspt_dev_download", "rspt_last_error", "rspt_last_counters", "rspt_bvh_build", "rspt_bvh_last_error",
            "rspt_bvh_build_gpu", "rspt_bvh_build_bounds", "rspt_comm_unique_id", "rspt_comm_init", "rspt_comm_destroy", "rspt_light_distribution", "rspt_libm",
            "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library", "rspt_realistic_camera_setup",
-           "rspt_camera_rays")
+           "rspt_camera_rays", "rspt_quadric_intersect")
 
 
 def tree_source_hash():
@@ -86,6 +86,7 @@ def lib():
         L.rspt_motion_bounds.argtypes = [vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, vp]
         L.rspt_realistic_camera_setup.argtypes = [vp, u32, C.c_float, C.c_float, C.c_float, u32, vp, vp, i32]
         L.rspt_camera_rays.argtypes = [vp, vp, u64, vp]
+        L.rspt_quadric_intersect.argtypes = [u32, vp, u64, vp]
         L.rspt_source_hash.restype = C.c_char_p
         L.rspt_comm_library.restype = C.c_char_p
         L.rspt_comm_unique_id.argtypes = [vp]
@@ -250,6 +251,20 @@ def leaf_lobe(records, wo, wi, u):
     out = np.empty_like(x)
     _check(lib().rspt_libm(14, x.ctypes.data, None, n, out.ctypes.data))
     return out[:, :13]
+
+
+def quadric_intersect(shape, records, o, d, t_max):
+    """rspt_quadric_intersect (ABI 27): shape = abi.MESH_SPHERE | MESH_DISK | MESH_CYLINDER, records of SPHERE_DT / DISK_DT / CYLINDER_DT, rays (o, d, t_max)
+    -> (n, 64): intersect's result, t, p, p_error, n, uv, dpdu, dpdv, dndu, dndv, the shading frame; [:, 43] = intersect_p's result"""
+    n = len(records)
+    w = np.ascontiguousarray(records).view(np.float32).reshape(n, -1)
+    x = np.zeros((n, 64), np.float32)
+    x[:, :w.shape[1]] = w
+    k = w.shape[1]
+    x[:, k:k + 3], x[:, k + 3:k + 6], x[:, k + 6] = o, d, t_max
+    out = np.empty_like(x)
+    _check(lib().rspt_quadric_intersect(int(shape), x.ctypes.data, n, out.ctypes.data))
+    return out
 
 
 def light_distribution(dscene, strategy, p):

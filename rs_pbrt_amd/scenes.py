@@ -527,7 +527,9 @@ class SceneBuilder:
         self.objects = {}            # name -> index
         self.cur_object = -1
         self.instances = []          # (object index, Transform primitive_to_world)
-        self.decl = []               # render_options.primitives order: ("mesh", m) | ("inst", k) | ("sphere", k)
+        self.decl = []               # render_options.primitives order: ("mesh", m) | ("inst", k) | ("sphere", k) | ("disk", k) | ("cylinder", k)
+        self.disks = []              # Shape "disk" (ABI 27): (rspt_disk record, material, emit, declaration parameters)
+        self.cylinders = []          # Shape "cylinder" (ABI 27): likewise
         self.spheres = []            # Shape "sphere" (ABI 23): (rspt_sphere record, material, emit, declaration parameters)
 
     # ---- object instancing ----
@@ -744,6 +746,52 @@ class SceneBuilder:
                              dict(radius=float(radius), zmin=float(z0), zmax=float(z1), phimax=float(phimax), xf=xf)))
         return k
 
+    def _shape_common(self, rec, object_to_world, medium):
+        """the fields every quadric record shares: the two matrices, Transform::swaps_handedness (transform.rs:309-315) in f32, the media"""
+        xf = object_to_world if object_to_world is not None else Transform.identity()
+        rec["object_to_world"] = np.asarray(xf.m, F32).reshape(-1); rec["world_to_object"] = np.asarray(xf.m_inv, F32).reshape(-1)
+        m = np.asarray(xf.m, F32)
+        det = F32(F32(F32(m[0, 0] * F32(F32(m[1, 1] * m[2, 2]) - F32(m[1, 2] * m[2, 1]))) - F32(m[0, 1] * F32(F32(m[1, 0] * m[2, 2]) - F32(m[1, 2] * m[2, 0]))))
+                  + F32(m[0, 2] * F32(F32(m[1, 0] * m[2, 1]) - F32(m[1, 1] * m[2, 0]))))
+        rec["transform_swaps_handedness"] = int(det < 0)
+        rec["medium_inside"], rec["medium_outside"] = medium[0] or 0, medium[1] or 0
+        return xf
+
+    def add_disk(self, height=0.0, radius=1.0, innerradius=0.0, phimax=360.0, object_to_world=None, material=None, emit=None, two_sided=False, medium=(None, None)):
+        """Shape "disk" (api.rs make_shapes, shapes/disk.rs:50-72) under the CTM object_to_world: Disk::new's radians(clamp(phimax, 0, 360)) in f32.
+        Served as a surface wherever spheres are (add_sphere); an emissive disk (emit) is accepted by rspt_scene_create and refused by rspt_render."""
+        assert self.cur_object < 0, "disks inside ObjectBegin / ObjectEnd are not modelled (disks next to object instances are refused)"
+        if material is None:
+            material = abi.NO_MATERIAL
+        clamp = lambda v, a, b: a if v < a else (b if v > b else v)      # noqa: E731  clamp_t (pbrt.rs)
+        rec = np.zeros((), abi.DISK_DT)
+        xf = self._shape_common(rec, object_to_world, medium)
+        rec["height"], rec["radius"], rec["inner_radius"] = F32(height), F32(radius), F32(innerradius)
+        rec["phi_max"] = F32(F32(F32(math.pi) / F32(180)) * clamp(F32(phimax), F32(0), F32(360)))      # radians() pbrt.rs:143-146
+        k = len(self.disks)
+        self.decl.append(("disk", k))
+        self.disks.append((rec, material, None if emit is None else (np.array(emit, F32), bool(two_sided)),
+                           dict(height=float(height), radius=float(radius), innerradius=float(innerradius), phimax=float(phimax), xf=xf)))
+        return k
+
+    def add_cylinder(self, radius=1.0, zmin=-1.0, zmax=1.0, phimax=360.0, object_to_world=None, material=None, emit=None, two_sided=False, medium=(None, None)):
+        """Shape "cylinder" (api.rs make_shapes, shapes/cylinder.rs:53-75): Cylinder::new's min / max of zmin, zmax and its radians(clamp(phimax, 0, 360)) in f32.
+        Served and refused as add_disk says."""
+        assert self.cur_object < 0, "cylinders inside ObjectBegin / ObjectEnd are not modelled (cylinders next to object instances are refused)"
+        if material is None:
+            material = abi.NO_MATERIAL
+        clamp = lambda v, a, b: a if v < a else (b if v > b else v)      # noqa: E731
+        rec = np.zeros((), abi.CYLINDER_DT)
+        xf = self._shape_common(rec, object_to_world, medium)
+        z0, z1 = F32(zmin), F32(zmax)
+        rec["radius"], rec["z_min"], rec["z_max"] = F32(radius), min(z0, z1), max(z0, z1)
+        rec["phi_max"] = F32(F32(F32(math.pi) / F32(180)) * clamp(F32(phimax), F32(0), F32(360)))
+        k = len(self.cylinders)
+        self.decl.append(("cylinder", k))
+        self.cylinders.append((rec, material, None if emit is None else (np.array(emit, F32), bool(two_sided)),
+                               dict(radius=float(radius), zmin=float(zmin), zmax=float(zmax), phimax=float(phimax), xf=xf)))
+        return k
+
     def add_quad(self, p, material, **kw):
         return self.add_mesh(np.array(p, F32), [[0, 1, 2], [0, 2, 3]], material, **kw)
 
@@ -848,7 +896,7 @@ class SceneBuilder:
         With object instances the top-level aggregate is built over (top-level triangles in declaration order, then the
         TransformedPrimitives in declaration order) from their world bounds by rspt_bvh_build_bounds; every object with more
         than one triangle gets its own BVHAccel from bvh_builder (api.rs:3046-3094)."""
-        if self.spheres:
+        if self.spheres or self.disks or self.cylinders:
             return self._finish_spheres(max_prims_in_node, instancing)
         P = np.ascontiguousarray(np.concatenate(self.P), F32)
         tri = np.ascontiguousarray(np.concatenate(self.tris), np.uint32)
@@ -977,39 +1025,44 @@ class SceneBuilder:
         tri = np.ascontiguousarray(np.concatenate(self.tris), np.uint32) if self.tris else np.zeros((0, 3), np.uint32)
         tri_mesh = np.concatenate(self.tri_mesh) if self.tri_mesh else np.zeros(0, np.uint32)
         first_tri_of_mesh = np.concatenate([[0], np.cumsum([len(t) for t in self.tris])]).astype(np.int64)
-        in_tri, in_sph = [], []
+        # (ABI 27: a disk or a cylinder is one primitive as a sphere is; in_kind says which list in_sph indexes)
+        shapes = {"sphere": (0, self.spheres, abi.MESH_SPHERE, sphere_world_bound), "disk": (1, self.disks, abi.MESH_DISK, disk_world_bound),
+                  "cylinder": (2, self.cylinders, abi.MESH_CYLINDER, cylinder_world_bound)}
+        by_kind = {v[0]: v for v in shapes.values()}
+        in_tri, in_sph, in_kind = [], [], []
         for kind, ref in self.decl:
             if kind == "mesh":
                 nt = len(self.tris[ref])
-                in_tri.append(np.arange(first_tri_of_mesh[ref], first_tri_of_mesh[ref] + nt)); in_sph.append(np.full(nt, -1))
+                in_tri.append(np.arange(first_tri_of_mesh[ref], first_tri_of_mesh[ref] + nt)); in_sph.append(np.full(nt, -1)); in_kind.append(np.full(nt, -1))
             else:
-                in_tri.append(np.array([-1])); in_sph.append(np.array([ref]))
-        in_tri, in_sph = np.concatenate(in_tri).astype(np.int64), np.concatenate(in_sph).astype(np.int64)
+                in_tri.append(np.array([-1])); in_sph.append(np.array([ref])); in_kind.append(np.array([shapes[kind][0]]))
+        in_tri, in_sph, in_kind = np.concatenate(in_tri).astype(np.int64), np.concatenate(in_sph).astype(np.int64), np.concatenate(in_kind).astype(np.int64)
         bounds = np.zeros((len(in_tri), 6), F32)
         tsel = in_tri >= 0
         tv = P[tri[in_tri[tsel]]]
         bounds[tsel, :3], bounds[tsel, 3:] = tv.min(1), tv.max(1)
         for row in np.nonzero(~tsel)[0]:
-            bounds[row, :3], bounds[row, 3:] = sphere_world_bound(self.spheres[in_sph[row]][0])
+            _, recs, _, bound_of = by_kind[in_kind[row]]
+            bounds[row, :3], bounds[row, 3:] = bound_of(recs[in_sph[row]][0])
         nodes, ordered = lib.bvh_build_bounds(bounds, max_prims_in_node)
         n = len(bounds)
         prims = np.zeros(n, abi.PRIM_DT)
         mesh_mat = np.array(self.mesh_material, np.uint32)
-        slot_tri, slot_sph = in_tri[ordered], in_sph[ordered]
+        slot_tri, slot_sph, slot_kind = in_tri[ordered], in_sph[ordered], in_kind[ordered]
         ts = slot_tri >= 0
         prims["v"][ts] = tri[slot_tri[ts]]
         prims["mesh"][ts] = tri_mesh[slot_tri[ts]]
         prims["material"][ts] = mesh_mat[tri_mesh[slot_tri[ts]]]
         prims["v"][~ts, 0] = slot_sph[~ts].astype(np.uint32)
-        prims["mesh"][~ts] = abi.MESH_SPHERE
-        prims["material"][~ts] = [self.spheres[k][1] for k in slot_sph[~ts]]
+        prims["mesh"][~ts] = [by_kind[q][2] for q in slot_kind[~ts]]
+        prims["material"][~ts] = [by_kind[q][1][k][1] for q, k in zip(slot_kind[~ts], slot_sph[~ts])]
         prims["area_light"] = -1
         # lights in shape-declaration order (one DiffuseAreaLight per emissive triangle or sphere, api.rs:2810-2852)
         slot_of_input = np.empty(n, np.int64)
         slot_of_input[ordered] = np.arange(n)
         lights_in = []
         for i in range(n):
-            emit = self.mesh_emit[tri_mesh[in_tri[i]]] if in_tri[i] >= 0 else self.spheres[in_sph[i]][2]
+            emit = self.mesh_emit[tri_mesh[in_tri[i]]] if in_tri[i] >= 0 else by_kind[in_kind[i]][1][in_sph[i]][2]
             if emit is not None:
                 prims["area_light"][slot_of_input[i]] = len(lights_in)
                 lights_in.append((slot_of_input[i], emit))
@@ -1027,11 +1080,24 @@ class SceneBuilder:
                      textures=np.array(self.textures, abi.TEXTURE_DT) if self.textures else None, images=self.images,
                      media=np.array(self.media, abi.MEDIUM_DT) if self.media else None,
                      instancing={"reference": abi.INSTANCING_REFERENCE, "fixed": abi.INSTANCING_FIXED}[instancing], builder=self,
-                     spheres=np.array([sp[0] for sp in self.spheres], abi.SPHERE_DT))
+                     spheres=np.array([sp[0] for sp in self.spheres], abi.SPHERE_DT),
+                     disks=np.array([q[0] for q in self.disks], abi.DISK_DT), cylinders=np.array([q[0] for q in self.cylinders], abi.CYLINDER_DT))
 
 
 def sphere_world_bound(rec):
     """Sphere::world_bound (sphere.rs:85-102): object_to_world.transform_bounds of ((-r, -r, z_min), (r, r, z_max))"""
+    r = F32(rec["radius"])
+    return _transform_bounds(np.asarray(rec["object_to_world"], F32).reshape(4, 4), np.array([-r, -r, rec["z_min"]], F32), np.array([r, r, rec["z_max"]], F32))
+
+
+def disk_world_bound(rec):
+    """Disk::world_bound (disk.rs:74-91): object_to_world.transform_bounds of ((-r, -r, h), (r, r, h))"""
+    r, h = F32(rec["radius"]), F32(rec["height"])
+    return _transform_bounds(np.asarray(rec["object_to_world"], F32).reshape(4, 4), np.array([-r, -r, h], F32), np.array([r, r, h], F32))
+
+
+def cylinder_world_bound(rec):
+    """Cylinder::world_bound (cylinder.rs:77-94): object_to_world.transform_bounds of ((-r, -r, z_min), (r, r, z_max))"""
     r = F32(rec["radius"])
     return _transform_bounds(np.asarray(rec["object_to_world"], F32).reshape(4, 4), np.array([-r, -r, rec["z_min"]], F32), np.array([r, r, rec["z_max"]], F32))
 
@@ -1056,9 +1122,11 @@ class Scene:
     """Flattened scene arrays + the ctypes rspt_scene_desc pointing at them."""
 
     def __init__(self, nodes, prims, meshes, P, N, UV, materials, lights, S=None, envmaps=(), textures=None, images=(),
-                 objects=None, instances=None, n_top=None, instancing=abi.INSTANCING_REFERENCE, builder=None, media=None, spheres=None):
+                 objects=None, instances=None, n_top=None, instancing=abi.INSTANCING_REFERENCE, builder=None, media=None, spheres=None, disks=None, cylinders=None):
         self.media = media if media is not None else np.zeros(0, abi.MEDIUM_DT)
         self.spheres = spheres if spheres is not None else np.zeros(0, abi.SPHERE_DT)   # ABI 23
+        self.disks = disks if disks is not None else np.zeros(0, abi.DISK_DT)                  # ABI 27
+        self.cylinders = cylinders if cylinders is not None else np.zeros(0, abi.CYLINDER_DT)
         self.builder = builder  # declaration-order view of the scene (tools/export_pbrt.py)
         self.nodes, self.prims, self.meshes, self.P, self.N, self.UV, self.S = nodes, prims, meshes, P, N, UV, S
         self.objects = objects if objects is not None else np.zeros(0, abi.OBJECT_DT)
@@ -1083,7 +1151,8 @@ class Scene:
                                   p(self.textures), len(self.textures),
                                   C.addressof(self._img_structs) if self.images else None, len(self.images),
                                   p(self.objects), len(self.objects), p(self.instances), len(self.instances),
-                                  self.n_top[0], self.n_top[1], instancing, len(self.media), p(self.media), p(self.spheres), len(self.spheres), 0)
+                                  self.n_top[0], self.n_top[1], instancing, len(self.media), p(self.media), p(self.spheres), len(self.spheres), 0,
+                                  p(self.disks), len(self.disks), 0, p(self.cylinders), len(self.cylinders), 0)
 
     def set_instancing(self, mode):
         """"reference" | "fixed" (rspt_scene_desc.instancing_mode); takes effect at the next DeviceScene / oracle call"""

@@ -1,10 +1,10 @@
-//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 26) one to one.
+//! src/gpu/ffi.rs — the `extern "C"` block for librspt.so, mirroring include/rspt.h (ABI version 27) one to one.
 //! Uncompiled source for a maintainer (the image this repo is built in has no Rust toolchain); struct layouts are checked
 //! from the C side by tests/test_abi.py, so a mismatch here shows up as a wrong `size_of` against the table in INTEGRATION.md §2.
 #![allow(dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RSPT_ABI_VERSION: c_int = 26;
+pub const RSPT_ABI_VERSION: c_int = 27;
 pub const RSPT_CAMERA_PERSPECTIVE: u32 = 0;   // ABI 25: rspt_render_desc.camera_kind
 pub const RSPT_CAMERA_ORTHOGRAPHIC: u32 = 1;
 pub const RSPT_CAMERA_ENVIRONMENT: u32 = 2;
@@ -12,6 +12,8 @@ pub const RSPT_CAMERA_REALISTIC: u32 = 3;     // ABI 26
 pub const RSPT_MAX_LENS_ELEMENTS: u32 = 32;
 pub const RSPT_MESH_INSTANCE: u32 = 0xffff_ffff;
 pub const RSPT_MESH_SPHERE: u32 = 0xffff_fffe;   // ABI 23: v[0] = index into spheres
+pub const RSPT_MESH_DISK: u32 = 0xffff_fffd;     // ABI 27: v[0] = index into disks
+pub const RSPT_MESH_CYLINDER: u32 = 0xffff_fffc; // ABI 27: v[0] = index into cylinders
 pub const RSPT_NO_MATERIAL: u32 = 0xffff_ffff;
 
 #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -26,6 +28,13 @@ pub struct RsptMesh { pub has_n: u32, pub has_s: u32, pub has_uv: u32, pub flip:
 pub struct RsptSphere { pub object_to_world: [f32; 16], pub world_to_object: [f32; 16], pub radius: f32, pub z_min: f32, pub z_max: f32,
                         pub theta_min: f32, pub theta_max: f32, pub phi_max: f32, pub reverse_orientation: u32, pub transform_swaps_handedness: u32,
                         pub medium_inside: u32, pub medium_outside: u32 }   // 168 B
+/// rspt_disk / rspt_cylinder (ABI 27): what Disk (shapes/disk.rs:17-28) and Cylinder (shapes/cylinder.rs:18-30) hold, as their new() left it
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RsptDisk { pub object_to_world: [f32; 16], pub world_to_object: [f32; 16], pub height: f32, pub radius: f32, pub inner_radius: f32, pub phi_max: f32,
+                      pub reverse_orientation: u32, pub transform_swaps_handedness: u32, pub medium_inside: u32, pub medium_outside: u32 }   // 160 B
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RsptCylinder { pub object_to_world: [f32; 16], pub world_to_object: [f32; 16], pub radius: f32, pub z_min: f32, pub z_max: f32, pub phi_max: f32,
+                          pub reverse_orientation: u32, pub transform_swaps_handedness: u32, pub medium_inside: u32, pub medium_outside: u32 }   // 160 B
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RsptMedium { pub kind: u32, pub sigma_a: [f32; 3], pub sigma_s: [f32; 3], pub g: f32,                 // kind 1 = HomogeneousMedium
                         pub nx: i32, pub ny: i32, pub nz: i32, pub pad: u32, pub density: *const f32, pub world_to_medium: [f32; 16] }   // kind 2 = GridDensityMedium
@@ -61,6 +70,8 @@ pub struct RsptInstance { pub object: u32, pub to_world: [f32; 16], pub from_wor
     pub objects: *const RsptObject, pub n_objects: u32, pub instances: *const RsptInstance, pub n_instances: u32,
     pub n_top_nodes: u64, pub n_top_prims: u64, pub instancing_mode: u32, pub n_media: u32, pub media: *const RsptMedium,
     pub spheres: *const RsptSphere, pub n_spheres: u32, pub pad_spheres: u32,   // ABI 23
+    pub disks: *const RsptDisk, pub n_disks: u32, pub pad_disks: u32,           // ABI 27
+    pub cylinders: *const RsptCylinder, pub n_cylinders: u32, pub pad_cylinders: u32,
 }
 /// rspt_lens_element (ABI 26): realistic.rs:27-33 LensElementInterface, metres
 #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -107,6 +118,7 @@ extern "C" {
     pub fn rspt_comm_init(rank: i32, world: i32, id: *const u8) -> c_int;
     pub fn rspt_comm_destroy() -> c_int;
     pub fn rspt_comm_library() -> *const c_char;                                   // which librccl the calls above are bound to (ABI 21)
+    pub fn rspt_quadric_intersect(shape: u32, x: *const f32, n: u64, out: *mut f32) -> c_int;   // stage hook (ABI 27): Sphere / Disk / Cylinder ::intersect, 64 floats per element
     pub fn rspt_source_hash() -> *const c_char;                                    // hash of the kernel sources compiled into the library (ABI 21)
     // AnimatedTransform::motion_bounds (transform.rs:2147-2210) on the host, for a caller that builds the top-level tree itself; the shim passes rs_pbrt's own BVH and
     // does not need it (ABI 21)

@@ -3,7 +3,7 @@
 //! repo is built in); it is written against rs_pbrt v0.9.12 plus the getters of rust_shim/rs_pbrt.patch.  Everything not covered
 //! returns Err and `SamplerIntegrator::render` keeps its CPU tile loop (src/core/integrator.rs:70-220).
 //!
-//! Covered: triangle meshes (Shape::Trngl) and spheres (Shape::Sphr; not next to object instances, and a frame with an emissive sphere, or one
+//! Covered: triangle meshes (Shape::Trngl), disks and cylinders (Shape::Dsk, Shape::Clndr, ABI 27: served and refused as spheres are) and spheres (Shape::Sphr; not next to object instances, and a frame with an emissive sphere, or one
 //! rendered by another integrator than path / ao or with a pixel sampler, comes back Err from rspt_render) under a BVHAccel aggregate, object instances (Primitive::Transformed, static or moving),
 //! matte / plastic / mirror / glass (smooth and rough) / metal / substrate / uber / translucent / mix (handed over as their
 //! parameters — one texture reference each, rspt_material_desc; the library assembles the lobes), diffuse area / point / spot / distant / infinite lights (the light's own MIP
@@ -59,6 +59,7 @@ type FloatTex = Arc<dyn Texture<Float> + Sync + Send>;
 #[derive(Default)]
 struct Flat {
     nodes: Vec<RsptBvhNode>, prims: Vec<RsptPrim>, meshes: Vec<RsptMesh>, spheres: Vec<RsptSphere>,   // spheres: ABI 23
+    disks: Vec<RsptDisk>, cylinders: Vec<RsptCylinder>,   // ABI 27
     p: Vec<f32>, n: Vec<f32>, s: Vec<f32>, uv: Vec<f32>, any_n: bool, any_s: bool, any_uv: bool,
     materials: Vec<RsptMaterialDesc>, lights: Vec<RsptLight>,
     objects: Vec<RsptObject>, instances: Vec<RsptInstance>,
@@ -238,8 +239,35 @@ impl Flat {
                                                    transform_swaps_handedness: sph.transform_swaps_handedness as u32, medium_inside, medium_outside });
                     self.prims.push(RsptPrim { v: [(self.spheres.len() - 1) as u32, 0, 0], mesh: RSPT_MESH_SPHERE, material, area_light });
                 }
+                Primitive::Geometric(g) if matches!(&*g.shape, Shape::Dsk(_) | Shape::Clndr(_)) => {
+                    // a GeometricPrimitive over a Disk or a Cylinder (ABI 27): what the shape holds (disk.rs:17-28, cylinder.rs:18-30) -> rspt_disk / rspt_cylinder, the
+                    // primitive -> an rspt_prim with mesh = RSPT_MESH_DISK / RSPT_MESH_CYLINDER and v[0] = the record's index.  Lights pair up as for a sphere;
+                    // rspt_render refuses an emissive one, so such a frame stays on the CPU loop.
+                    if !top { return Err("disk or cylinder inside an object instance".into()); }   // (the library refuses them next to instances)
+                    let (medium_inside, medium_outside) = match &g.medium_interface { Some(i) => (self.medium(&i.inside)?, self.medium(&i.outside)?), None => (0, 0) };
+                    let area_light = match &g.area_light {
+                        Some(al) => lights.iter().position(|l| Arc::ptr_eq(l, al)).map(|i| i as i32).unwrap_or(-1),
+                        None => -1,
+                    };
+                    let material = self.material(&g.material)?;
+                    match &*g.shape {
+                        Shape::Dsk(d) => {
+                            self.disks.push(RsptDisk { object_to_world: m16(&d.object_to_world.m), world_to_object: m16(&d.world_to_object.m), height: d.height,
+                                                       radius: d.radius, inner_radius: d.inner_radius, phi_max: d.phi_max, reverse_orientation: d.reverse_orientation as u32,
+                                                       transform_swaps_handedness: d.transform_swaps_handedness as u32, medium_inside, medium_outside });
+                            self.prims.push(RsptPrim { v: [(self.disks.len() - 1) as u32, 0, 0], mesh: RSPT_MESH_DISK, material, area_light });
+                        }
+                        Shape::Clndr(c) => {
+                            self.cylinders.push(RsptCylinder { object_to_world: m16(&c.object_to_world.m), world_to_object: m16(&c.world_to_object.m), radius: c.radius,
+                                                               z_min: c.z_min, z_max: c.z_max, phi_max: c.phi_max, reverse_orientation: c.reverse_orientation as u32,
+                                                               transform_swaps_handedness: c.transform_swaps_handedness as u32, medium_inside, medium_outside });
+                            self.prims.push(RsptPrim { v: [(self.cylinders.len() - 1) as u32, 0, 0], mesh: RSPT_MESH_CYLINDER, material, area_light });
+                        }
+                        _ => unreachable!(),
+                    }
+                }
                 Primitive::Geometric(g) => {
-                    let tri = match &*g.shape { Shape::Trngl(t) => t, _ => return Err("shape other than triangles and spheres".into()) };
+                    let tri = match &*g.shape { Shape::Trngl(t) => t, _ => return Err("shape other than triangles, spheres, disks and cylinders".into()) };
                     let (mesh, first) = self.mesh(tri.mesh(), &g.medium_interface)?; // Triangle.mesh getter: rs_pbrt.patch (triangle.rs:85)
                     let vi = &tri.mesh().vertex_indices[3 * tri.id as usize..3 * tri.id as usize + 3];
                     let area_light = match &g.area_light {                         // the reference compares these pointers (integrator.rs:540-543)
@@ -480,6 +508,8 @@ pub fn render_path(integ: &SamplerIntegrator, scene: &Scene) -> Result<(), Strin
         n_top_nodes, n_top_prims, instancing_mode: (std::env::var_os("RSPT_INSTANCING_FIXED").is_some()) as u32,
         n_media: f.media.len() as u32, media: if f.media.is_empty() { std::ptr::null() } else { f.media.as_ptr() },
         spheres: if f.spheres.is_empty() { std::ptr::null() } else { f.spheres.as_ptr() }, n_spheres: f.spheres.len() as u32, pad_spheres: 0,
+        disks: if f.disks.is_empty() { std::ptr::null() } else { f.disks.as_ptr() }, n_disks: f.disks.len() as u32, pad_disks: 0,
+        cylinders: if f.cylinders.is_empty() { std::ptr::null() } else { f.cylinders.as_ptr() }, n_cylinders: f.cylinders.len() as u32, pad_cylinders: 0,
     };
     unsafe {
         if rspt_abi_version() != RSPT_ABI_VERSION { return Err("librspt.so ABI version mismatch".into()); }

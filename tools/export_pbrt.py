@@ -213,10 +213,10 @@ def export(sc, path, look_at, fov, xres, yres, spp, max_depth=5, sampler="sobol"
             if sb.mesh_object[m] == o:
                 out += mesh_block(m, "  ")
         out.append("ObjectEnd")
-    def sphere_block(k):
-        """Shape "sphere" under its own CTM: one Transform directive, so rs_pbrt derives world_to_object by Matrix4x4::inverse — the builder's
+    def sphere_block(k, what="sphere"):
+        """Shape "sphere" (or, ABI 27, "disk" / "cylinder") under its own CTM: one Transform directive, so rs_pbrt derives world_to_object by Matrix4x4::inverse — the builder's
         Transform must be Transform(m); an area light's AreaLightSource comes before the shape (api.rs make_shapes / pbrt_shape)"""
-        _rec, mat, emit, prm = sb.spheres[k]
+        _rec, mat, emit, prm = {"sphere": sb.spheres, "disk": sb.disks, "cylinder": sb.cylinders}[what][k]
         from rs_pbrt_amd import scenes as _sc
         xf = prm["xf"]
         assert np.array_equal(np.asarray(xf.m_inv, np.float32), np.asarray(_sc.Transform(xf.m).m_inv, np.float32)), "sphere transform was not built as Transform(m)"
@@ -230,17 +230,20 @@ def export(sc, path, look_at, fov, xres, yres, spp, max_depth=5, sampler="sobol"
             blk.append('  MediumInterface "%s" "%s"' % ("medium%d" % mi if mi else "", "medium%d" % mo if mo else ""))
         if emit is not None:
             blk.append('  AreaLightSource "diffuse" "rgb L" [%s] "bool twosided" ["%s"]' % (f(emit[0]), "true" if emit[1] else "false"))
-        blk += ["  " + text, "  Transform [%s]" % f(np.asarray(xf.m, np.float32).reshape(4, 4).T),
-                '  Shape "sphere" "float radius" [%s] "float zmin" [%s] "float zmax" [%s] "float phimax" [%s]' % (
-                    f(prm["radius"]), f(prm["zmin"]), f(prm["zmax"]), f(prm["phimax"])),
-                "AttributeEnd"]
+        if what == "disk":
+            shape = '  Shape "disk" "float height" [%s] "float radius" [%s] "float innerradius" [%s] "float phimax" [%s]' % (
+                f(prm["height"]), f(prm["radius"]), f(prm["innerradius"]), f(prm["phimax"]))
+        else:
+            shape = '  Shape "%s" "float radius" [%s] "float zmin" [%s] "float zmax" [%s] "float phimax" [%s]' % (
+                what, f(prm["radius"]), f(prm["zmin"]), f(prm["zmax"]), f(prm["phimax"]))
+        blk += ["  " + text, "  Transform [%s]" % f(np.asarray(xf.m, np.float32).reshape(4, 4).T), shape, "AttributeEnd"]
         return blk
 
     for what, k in sb.decl:
         if what == "mesh":
             out += mesh_block(k)
-        elif what == "sphere":
-            out += sphere_block(k)
+        elif what in ("sphere", "disk", "cylinder"):
+            out += sphere_block(k, what)
         else:
             obj, xf, xf_end, _times = sb.instances[k]
             from rs_pbrt_amd import scenes as _sc

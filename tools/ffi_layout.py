@@ -15,7 +15,7 @@ PRIM = {"f32": (4, 4), "u32": (4, 4), "i32": (4, 4), "u16": (2, 2), "i16": (2, 2
 NAMES = {"RsptBvhNode": "rspt_bvh_node", "RsptPrim": "rspt_prim", "RsptMesh": "rspt_mesh", "RsptMedium": "rspt_medium", "RsptMaterialDesc": "rspt_material_desc",
          "RsptImage": "rspt_image", "RsptTexture": "rspt_texture", "RsptLight": "rspt_light", "RsptEnvMap": "rspt_envmap", "RsptObject": "rspt_object",
          "RsptInstance": "rspt_instance", "RsptSceneDesc": "rspt_scene_desc", "RsptSamplerTables": "rspt_sampler_tables", "RsptRenderDesc": "rspt_render_desc",
-         "RsptStats": "rspt_stats", "RsptSphere": "rspt_sphere", "RsptLensElement": "rspt_lens_element"}
+         "RsptStats": "rspt_stats", "RsptSphere": "rspt_sphere", "RsptDisk": "rspt_disk", "RsptCylinder": "rspt_cylinder", "RsptLensElement": "rspt_lens_element"}
 
 
 def rust_structs(path):
