@@ -28,7 +28,11 @@ uint32_t trace_grid() { return grid_for((uint32_t)env_size("RSPT_TRACE_BLOCKS_PE
 #ifndef RSPT_PW_ENTER
 #define RSPT_PW_ENTER 24   // C5 stand-in, every instance moving (profiles/r06_c5_enter_sweep.txt): 1 -> 142, 8 -> 170, 16 -> 182, 24 -> 183, 32 -> 180 Msamples/s
 #endif
-// What one trace launch reads and writes.  Every field defaults to "absent": a call site names what it uses.
+#ifndef RSPT_PW_LEAF_ANY_Q_DEFAULT
+#define RSPT_PW_LEAF_ANY_Q_DEFAULT 16   // parked lanes that start a leaf phase of k_trace_w4q (trace_w4q.h).  C2 frame, one box, one process (profiles/shadow_defer_ab.txt section 6):
+                                        // 8 -> 554.9 / 553.4 / 554.7 / 554.4, 16 -> 561.6 / 561.3, 24 -> 561.9, 32 -> 556.6 / 556.8, 48 -> 527.3 Msamples/s; the C3 stand-in does not resolve 8 / 16 / 32
+#endif
+// What one trace launch reads and writes. Every field defaults to "absent": a call site names what it uses.
 struct TraceCall {
     const uint32_t* queue = nullptr; const uint32_t* count_ptr = nullptr; uint32_t count_imm = 0;   // the queue entries to trace; their number on the device, or known to the host
     uint32_t* cursor = nullptr;                                  // the persistent kernels' fetch cursor (QueueCounts: the overflow word sits two after it)
@@ -138,8 +142,11 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
         const char* q_env = getenv("RSPT_ANY_Q");
         const bool use_q = c.force_any_q >= 0 ? c.force_any_q != 0 : (q_env && *q_env ? atoi(q_env) != 0 : s->any_q_choice > 0);
         if (use_q && which >= 2 && s->w4q && !(s->w4_root & RSPT_REF_LEAF) && c.ra == c.rb && env_size("RSPT_W4_SHAPE", RSPT_W4_SHAPE_DEFAULT) == 0 && !xcur && spill_rows == RSPT_W4_SPILL) {
+            // the leaf-phase threshold of this kernel is its own (RSPT_PW_LEAF_ANY_Q): its leaf phase is the any-hit one (no t_max to hand back to the node steps), so
+            // parked lanes can wait for a fuller phase than the closest-hit kernels' RSPT_PW_LEAF = 8 allows — RSPT_PW_LEAF_ANY_Q_DEFAULT above
+            const int q_leaf = (int)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_LEAF_ANY_Q", RSPT_PW_LEAF_ANY_Q_DEFAULT), 1), 64);
             hipLaunchKernelGGL((k_trace_w4q<OUT_MODE>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->w4q, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                               c.ra, c.occ, c.hits, reinterpret_cast<uint32_t*>(p.spill), p.refill, p.leaf, s->w4_top,
+                               c.ra, c.occ, c.hits, reinterpret_cast<uint32_t*>(p.spill), p.refill, q_leaf, s->w4_top,
                                pw_chunk | (env_size("RSPT_ANY_Q_LATE", 1) != 0 ? 2u : 0u) /* bit 1: the exact leaf-box test only behind a triangle hit (trace_w4q.h) */, s->leaf_boxes);
             return;
         }

@@ -40,6 +40,11 @@ static_assert(sizeof(Quad4Node) == 64, "Quad4Node is four 16-byte loads");
 #define RSPT_W4Q_ORDERED 0   // 1: the four slots of a record in the reference's near-first order (A/B, tools/ab_build.sh AB_DEFS=-DRSPT_W4Q_ORDERED=1)
 #endif
 
+#ifdef RSPT_W4Q_COUNT   // timing-only A/B build (tools/ab_build.sh AB_DEFS=-DRSPT_W4Q_COUNT, tools/w4q_lane_count.py): lane occupancy of the two phases, summed over every launch
+// {node steps issued, lanes active in them, leaf phases issued, lanes active in them, rays ended occluded, rays ended unoccluded, node steps of the occluded rays, leaf visits of the occluded rays}
+static __device__ unsigned long long g_w4q_count[8];   // one copy per translation unit: read where the kernels are instantiated (tu_w4q.hip)
+#endif
+
 template <int OUT_MODE>
 __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const Quad4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
@@ -83,8 +88,16 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const 
     uint32_t negbits = 0;  // bit a = dir_is_neg[a]; bits 4..6: axes the grid test leaves out
     uint32_t sp = 0, cur = RSPT_NONE, leaf = RSPT_NONE;
     uint32_t entry = 0, qpos = 0;
+#ifdef RSPT_W4Q_COUNT
+    unsigned long long cw_steps = 0, cw_phases = 0;                                                               // wave-uniform
+    unsigned long long cl_steps = 0, cl_leaves = 0, cl_occ = 0, cl_un = 0, cl_steps_occ = 0, cl_leaves_occ = 0;   // per lane, added up at wave exit
+    uint32_t ray_steps = 0, ray_leaves = 0;                                                                       // of the lane's current ray
+#endif
 
     auto finish = [&](bool occluded) {
+#ifdef RSPT_W4Q_COUNT
+        if (occluded) { cl_occ++; cl_steps_occ += ray_steps; cl_leaves_occ += ray_leaves; } else cl_un++;
+#endif
         if (OUT_MODE == 0) out_occ[entry] = occluded ? 1u : 0u;
         else {
             rspt_hit h;
@@ -124,6 +137,9 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const 
                     q_margin = 0x1.0p-19f * (q_scene + fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)));   // in position units; times |inv| of an axis = that axis's D
                     rs = ray_shear(d);
                     sp = 0; cur = RSPT_NONE; leaf = RSPT_NONE;
+#ifdef RSPT_W4Q_COUNT
+                    ray_steps = ray_leaves = 0;
+#endif
                     active = true;
                     // the root's own box (bvh.rs:480 on node 0), the reference's test
                     if (box_hit(root0, root1, f3{ox, oy, oz}, f3{ix, iy, iz}, negbits & 1u, negbits & 2u, negbits & 4u, t_max)) {
@@ -145,6 +161,10 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const 
 #pragma unroll 1
         for (int step = 0; step < RSPT_W4_STEPS; step++)
         if (active && leaf == RSPT_NONE) {
+#ifdef RSPT_W4Q_COUNT
+            if (lane == (uint32_t)__ffsll((long long)__ballot(1)) - 1u) cw_steps++;   // (kept by the step's first active lane; summed over the wave at exit)
+            cl_steps++; ray_steps++;
+#endif
             uint32_t ridx = cur;
             if (ridx == RSPT_NONE) {
                 if (sp == 0) finish(false);   // every box the ray reaches has been looked at: nothing stops it
@@ -260,6 +280,10 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const 
         if (parked) {
             const uint64_t running = __ballot(active && leaf == RSPT_NONE);
             if (__popcll(parked) >= leaf_thresh || running == 0) {
+#ifdef RSPT_W4Q_COUNT
+                if (lane == (uint32_t)__ffsll((long long)parked) - 1u) cw_phases++;
+                if (active && leaf != RSPT_NONE) { cl_leaves++; ray_leaves++; }
+#endif
                 if (active && leaf != RSPT_NONE) {
                     uint32_t offset = leaf & RSPT_W4_OFFSET_MASK, n_prims = ((leaf >> RSPT_W4_COUNT_SHIFT) & 15u) + 1u;
                     if (n_prims == 16u) {
@@ -293,6 +317,12 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const 
             }
         }
     }
+#ifdef RSPT_W4Q_COUNT
+    const unsigned long long adds[8] = {cw_steps, cl_steps, cw_phases, cl_leaves, cl_occ, cl_un, cl_steps_occ, cl_leaves_occ};
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (adds[k]) atomicAdd(&g_w4q_count[k], adds[k]);
+#endif
 }
 
 }  // namespace rspt
