@@ -11,9 +11,9 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <map>
+#include <memory>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -21,6 +21,8 @@
 
 #include "../../include/rspt.h"
 #include "material_assembly.h"
+#include "scene_materials.h"
+#include "scene_records.h"
 #include "camera_anim.h"
 #include "motion_bounds.h"
 #include "kernels.h"
@@ -263,7 +265,11 @@ struct rspt_scene_s {
         has_textures = m.textured;
         has_dynamic = m.dynamic;
     }
-    std::vector<void*> allocs;
+    std::vector<void*> allocs;        // every device allocation of the scene: freed with it
+    rspt_scene_s() = default;
+    rspt_scene_s(const rspt_scene_s&) = delete;
+    rspt_scene_s& operator=(const rspt_scene_s&) = delete;
+    ~rspt_scene_s() { for (void* p : allocs) (void)hipFree(p); }
     bool has_null_material = false;
     uint32_t n_materials = 0;
     bool has_alpha = false;           // some mesh carries an alpha / shadow-alpha mask (Triangle::intersect's alpha tests)
@@ -586,6 +592,158 @@ int render_impl(rspt_scene_s* s, const rspt_render_desc* d, float* film_host, vo
     return r.report(stats, t_start);
 }
 
+// ---- rspt_scene_create's device steps: each takes records that scene_records.h built on the host and uploads them; the scene owns what was uploaded ----
+template <class T>
+int upload(rspt_scene_s* s, const std::vector<T>& v, const T** out) { return upload(s, v.data(), v.size(), out); }
+#define UP(...) do { if ((rc = upload(s, __VA_ARGS__))) return rc; } while (0)
+
+// media: a grid medium's density goes to the device, its record gets the device pointer and 1 / max(density) (GridDensityMedium::new, grid.rs:44-55)
+int upload_media(rspt_scene_s* s, const rspt_scene_desc* d) {
+    int rc;
+    std::vector<rspt_medium> media(d->media, d->media + d->n_media);
+    for (rspt_medium& m : media) {
+        if (m.kind != RSPT_MEDIUM_GRID) continue;
+        const float inv_max = scene::grid_inv_max_density(m);
+        memcpy(&m.pad, &inv_max, sizeof inv_max);
+        const float* dens_d = nullptr;
+        UP(m.density, (size_t)m.nx * m.ny * m.nz, &dens_d);
+        m.density = dens_d;
+        s->dev.n_grid_media++;
+    }
+    UP(media, &s->dev.media);
+    s->dev.n_media = d->n_media;
+    return RSPT_OK;
+}
+
+// the two lobe sets with their slot tables; the texture tables when a material is textured (k_texture / per-path texture rows) or a mesh is alpha-masked
+int upload_materials(rspt_scene_s* s, const rspt_scene_desc* d, const scene::SceneMaterials& sm) {
+    int rc;
+    for (int v = 0; v < 2; v++) {
+        rspt_scene_s::MatSet& ms = s->mat_set[v];
+        ms.textured = sm.textured[v];
+        ms.dynamic = !sm.dyn[v].empty();
+        if (ms.dynamic) UP(sm.dyn[v], &ms.dyn);
+        UP(sm.mats[v], &ms.materials); UP(sm.bxdfs[v], &ms.bxdfs); UP(sm.slots[v], &ms.mat_slots); UP(sm.mflags[v], &ms.mat_flags);
+    }
+    s->select_materials(true);
+    if (!sm.textured[0] && !sm.textured[1] && !s->has_alpha) return RSPT_OK;
+    UP(d->textures, d->n_textures, &s->tex.textures);
+    std::vector<ImageDev> imgs;
+    std::vector<float> pool;
+    scene::build_image_pool(d, &imgs, &pool, &s->image_base);
+    UP(pool, &s->tex.texel_pool);
+    UP(imgs, &s->tex.images);
+    float lut[RSPT_EWA_LUT];
+    scene::ewa_weights(lut);
+    UP(lut, (size_t)RSPT_EWA_LUT, &s->tex.ewa_lut);
+    return RSPT_OK;
+}
+
+// Scene.infinite_lights and the environment maps: each map's pyramid, and its Distribution2D unless only projection / goniometric lights name it (ABI 24)
+int upload_envmaps(rspt_scene_s* s, const rspt_scene_desc* d) {
+    int rc;
+    const std::vector<uint32_t> inf = scene::infinite_lights(d);
+    s->dev.n_infinite = (uint32_t)inf.size();
+    UP(inf, &s->dev.infinite_lights);
+    std::vector<EnvMapDev> envs(d->n_envmaps);
+    for (uint32_t i = 0; i < d->n_envmaps; i++) {
+        const rspt_envmap& e = d->envmaps[i];
+        EnvMapDev& m = envs[i];
+        m.width = e.width; m.height = e.height; m.n_levels = e.n_levels; m.nu = e.dist_nu; m.nv = e.dist_nv;
+        UP(e.texels, scene::pyramid_offsets(e.width, e.height, e.n_levels, m.level_offset) * 3, &m.texels);
+        if (!e.dist_func) continue;   // the pyramid alone, the distribution pointers stay null
+        const scene::EnvDist dist = scene::build_env_dist(e);
+        m.marg_int = dist.marg_int;
+        UP(e.dist_func, (size_t)e.dist_nu * e.dist_nv, &m.cond_func); UP(dist.cdf, &m.cond_cdf);
+        UP(dist.fint, &m.cond_int); UP(dist.fint, &m.marg_func); UP(dist.mcdf, &m.marg_cdf);
+    }
+    UP(envs, &s->dev.envmaps);
+    return RSPT_OK;
+}
+
+// the four-box records (trace_w4.h) and, for the shadow rays of plain scenes, their quantised form with the leaf boxes (trace_w4q.h)
+int upload_w4(rspt_scene_s* s, const rspt_scene_desc* d, const scene::SceneFacts& f, const scene::W4Records& w4) {
+    int rc;
+    s->w4_root = w4.w4_root; s->w4_top = w4.w4_top; s->w4_ok = w4.w4_ok;
+    if (w4.w4_ok) UP(w4.recs, &s->w4);
+    UP(w4.big_leaves, &s->big_leaves);
+    // not for scenes with instances or alpha masks, nor with spheres, disks or cylinders: k_trace_w4q walks triangle leaves only, and launch_trace_sph never takes it
+    if (!s->w4 || f.instanced || f.any_alpha || d->n_spheres || d->n_disks || d->n_cylinders || env_size("RSPT_W4Q_BUILD", 1) == 0) return RSPT_OK;
+    std::vector<Quad4Node> q;
+    if (!scene::quantise_w4(w4.recs, &q)) return RSPT_OK;
+    UP(q, &s->w4q);
+    UP(scene::leaf_boxes(d), &s->leaf_boxes);
+    return RSPT_OK;
+}
+
+// the triangle records (k_build_tris) with the sphere / disk / cylinder slots behind them, and the in-line alpha masks they name
+int build_primitive_records(rspt_scene_s* s, const rspt_scene_desc* d, const scene::SceneFacts& f, const scene::W4Records& w4, const rspt_mesh* meshes_d, const float* P_d) {
+    int rc;
+    float4* tris = nullptr;
+    // a scene with spheres keeps them behind the triangle records (dev_sphere.h SphereDev, RSPT_SPHERE_F4 float4 each); disks and cylinders take sphere slots (ABI 27)
+    const uint64_t n_slots = (uint64_t)d->n_spheres + d->n_disks + d->n_cylinders;
+    hipError_t e = hipMalloc((void**)&tris, (d->n_prims * 3 + n_slots * RSPT_SPHERE_F4) * sizeof(float4));
+    if (e != hipSuccess) return fail(RSPT_E_NOMEM, "triangle records: %s", hipGetErrorString(e));
+    s->allocs.push_back(tris);
+    const uint32_t* inst_cont_d = nullptr, *mesh_mask_d = nullptr;
+    UP(w4.inst_cont, &inst_cont_d);
+    if (s->has_alpha && env_size("RSPT_ALPHA_SIMPLE", 1) != 0) {
+        const scene::AlphaMasks am = scene::build_alpha_masks(d, s->image_base, s->dev.tri_nuv != nullptr);
+        if (am.simple && !am.entries.empty()) {
+            UP(am.entries, &s->dev.alpha_masks); UP(am.mesh_mask, &mesh_mask_d);
+            s->alpha_simple = true;
+        }
+    }
+    hipLaunchKernelGGL(k_build_tris, dim3((uint32_t)((d->n_prims + 255) / 256)), dim3(256), 0, g.stream, s->dev.prims, meshes_d, P_d, (uint32_t)d->n_prims, tris, inst_cont_d, mesh_mask_d);
+    e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) return fail(RSPT_E_HIP, "k_build_tris: %s", hipGetErrorString(e));
+    if (d->n_spheres) {   // ABI 23 (k_build_tris wrote the sphere primitives' own records)
+        const std::vector<SphereDev> sph = scene::sphere_slots(d);
+        e = hipMemcpy(tris + 3 * d->n_prims, sph.data(), sph.size() * sizeof(SphereDev), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(RSPT_E_HIP, "sphere records: %s", hipGetErrorString(e));
+        s->has_spheres = true;
+        s->shade_features |= SF_SPHERE;
+        for (uint64_t i = 0; i < d->n_prims; i++)
+            if (d->prims[i].mesh == RSPT_MESH_SPHERE && d->prims[i].area_light != -1) s->has_sphere_light = true;
+    }
+    if (d->n_disks || d->n_cylinders) {   // ABI 27: every slot again with its kind
+        const std::vector<QuadricDev> q = scene::quadric_slots(d);
+        e = hipMemcpy(tris + 3 * d->n_prims, q.data(), q.size() * sizeof(QuadricDev), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(RSPT_E_HIP, "disk / cylinder records: %s", hipGetErrorString(e));
+        s->has_spheres = s->has_quadrics = true;
+        s->has_disks = d->n_disks != 0; s->has_cylinders = d->n_cylinders != 0;
+        s->quadric_kinds = s->has_disks && s->has_cylinders ? "disk and cylinder" : (s->has_disks ? "disk" : "cylinder");
+        if (f.disk_light || f.cylinder_light) {
+            s->quadric_light_kinds = f.disk_light && f.cylinder_light ? "disk and cylinder" : (f.disk_light ? "disk" : "cylinder");
+            s->quadric_light_what = f.disk_light && f.cylinder_light ? "disk area lights and cylinder area lights" : (f.disk_light ? "disk area lights" : "cylinder area lights");
+        }
+        s->shade_features |= SF_SPHERE | SF_QUADRIC;
+    }
+    s->dev.tris = tris;
+    if (s->w4_ok && s->w4 && !f.instanced && (!s->has_alpha || s->alpha_simple) && env_size("RSPT_SERIAL_W4", 1) != 0) {   // the per-lane kernels' traversal (trace_serial.h)
+        s->dev.w4 = s->w4; s->dev.w4_big = s->big_leaves; s->dev.w4_root = s->w4_root;
+    }
+    return RSPT_OK;
+}
+
+// InstDev records, and the keys of the moving instances
+int upload_instances(rspt_scene_s* s, const rspt_scene_desc* d, const scene::W4Records& w4) {
+    int rc;
+    std::vector<InstDev> ins;
+    std::vector<InstAnim> anims;
+    scene::build_instances(d, w4.obj_root, &ins, &anims);
+    if (!anims.empty()) {
+        if (s->has_alpha && !s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "moving object instances together with alpha-masked meshes in a scene whose records outgrow the four-box kernel");
+        UP(anims, &s->dev.inst_anim);
+        s->has_animated = true;
+        s->shade_features |= SF_ANIM;
+    }
+    UP(ins, &s->dev.inst);
+    s->dev.n_inst = d->n_instances;
+    s->dev.inst_fixed = d->instancing_mode == RSPT_INSTANCING_FIXED ? 1u : 0u;
+    return RSPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -765,498 +923,50 @@ int rspt_comm_destroy(void) {
 }
 
 int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
+    using namespace rspt::scene;
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!d || !out) return fail(RSPT_E_INVALID, "null argument");
     *out = nullptr;
-    if (d->n_prims > 0x7fffffffull || d->n_nodes > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "more than 2^31 primitives / nodes");
-    if ((d->n_nodes && !d->nodes) || (d->n_prims && (!d->prims || !d->meshes || !d->P)) || (d->n_materials && !d->materials) ||
-        (d->n_lights && !d->lights))
-        return fail(RSPT_E_INVALID, "null array with non-zero count");
-    if ((d->n_nodes == 0) != (d->n_prims == 0)) return fail(RSPT_E_INVALID, "nodes and prims must both be empty or both non-empty");
-    // ---- validate indices on the host (a bad scene must not fault the GPU) ----
-    bool has_null = false;
-    const bool instanced = d->n_instances > 0;
-    const uint64_t n_top_prims = instanced ? d->n_top_prims : d->n_prims, n_top_nodes = instanced ? d->n_top_nodes : d->n_nodes;
-    if (d->n_spheres && instanced) return fail(RSPT_E_UNSUPPORTED, "spheres together with object instances");   // (ABI 23: a follow-up)
-    if (d->n_disks && instanced) return fail(RSPT_E_UNSUPPORTED, "disks together with object instances");
-    if (d->n_cylinders && instanced) return fail(RSPT_E_UNSUPPORTED, "cylinders together with object instances");
-    if (instanced) {  // objects + instances behind the top-level aggregate
-        if (!d->instances || !d->objects || d->n_objects == 0) return fail(RSPT_E_INVALID, "instances without objects");
-        if (n_top_prims > d->n_prims || n_top_nodes > d->n_nodes || n_top_nodes == 0) return fail(RSPT_E_INVALID, "bad top-level aggregate range");
-        if (d->instancing_mode != RSPT_INSTANCING_REFERENCE && d->instancing_mode != RSPT_INSTANCING_FIXED) return fail(RSPT_E_INVALID, "bad instancing_mode");
-        for (uint32_t i = 0; i < d->n_objects; i++) {
-            const rspt_object& o = d->objects[i];
-            if (o.n_prims == 0 || o.first_prim < n_top_prims || o.first_prim + o.n_prims > d->n_prims) return fail(RSPT_E_INVALID, "object %u: primitive range", i);
-            if (o.n_nodes == 0 ? o.n_prims != 1 : (o.first_node < n_top_nodes || o.first_node + o.n_nodes > d->n_nodes)) return fail(RSPT_E_INVALID, "object %u: node range", i);
-        }
-        for (uint32_t i = 0; i < d->n_instances; i++) {
-            const rspt_instance& in = d->instances[i];
-            if (in.object >= d->n_objects) return fail(RSPT_E_INVALID, "instance %u: object index out of range", i);
-            for (int k = 0; k < 2; k++) {   // (rows 3 other than (0 0 0 1) are served: InstDev::m3 / mi3; a weight of 0 is where the reference asserts, transform.rs:747)
-                const float* m = k ? in.from_world : in.to_world;
-                if (!std::isfinite(m[12]) || !std::isfinite(m[13]) || !std::isfinite(m[14]) || !std::isfinite(m[15])) return fail(RSPT_E_INVALID, "instance %u: non-finite transform", i);
-                for (int j = 0; j < 12; j++) if (!(fabsf(m[j]) < RSPT_INF)) return fail(RSPT_E_INVALID, "instance %u: non-finite transform", i);
-            }
-        }
-    }
-    // ABI 23: spheres (dev_sphere.h)
-    if (d->n_spheres && !d->spheres) return fail(RSPT_E_INVALID, "null spheres with n_spheres > 0");
-    for (uint32_t i = 0; i < d->n_spheres; i++) {
-        const rspt_sphere& sp = d->spheres[i];
-        for (int k = 0; k < 16; k++)
-            if (!std::isfinite(sp.object_to_world[k]) || !std::isfinite(sp.world_to_object[k])) return fail(RSPT_E_INVALID, "sphere %u: non-finite transform", i);
-        if (!(sp.radius > 0.0f) || !std::isfinite(sp.radius) || !std::isfinite(sp.z_min) || !std::isfinite(sp.z_max) || !std::isfinite(sp.phi_max) ||
-            !std::isfinite(sp.theta_min) || !std::isfinite(sp.theta_max))
-            return fail(RSPT_E_INVALID, "sphere %u: radius must be positive and finite, z / theta / phi finite", i);
-        if (sp.medium_inside > d->n_media || sp.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "sphere %u: medium index out of range", i);
-    }
-    // ABI 27: disks and cylinders (dev_quadric.h)
-    if (d->n_disks && !d->disks) return fail(RSPT_E_INVALID, "null disks with n_disks > 0");
-    if (d->n_cylinders && !d->cylinders) return fail(RSPT_E_INVALID, "null cylinders with n_cylinders > 0");
-    if ((uint64_t)d->n_spheres + d->n_disks + d->n_cylinders > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "more than 2^31 spheres, disks and cylinders");
-    for (uint32_t i = 0; i < d->n_disks; i++) {
-        const rspt_disk& k = d->disks[i];
-        for (int j = 0; j < 16; j++)
-            if (!std::isfinite(k.object_to_world[j]) || !std::isfinite(k.world_to_object[j])) return fail(RSPT_E_INVALID, "disk %u: non-finite transform", i);
-        if (!std::isfinite(k.height) || !std::isfinite(k.radius) || !std::isfinite(k.inner_radius) || !std::isfinite(k.phi_max)) return fail(RSPT_E_INVALID, "disk %u: non-finite parameter", i);
-        if (!(k.radius > 0.0f)) return fail(RSPT_E_INVALID, "disk %u: radius must be positive", i);
-        if (k.radius == k.inner_radius) return fail(RSPT_E_INVALID, "disk %u: radius equals inner_radius (v divides by their difference)", i);
-        if (!(k.phi_max > 0.0f && k.phi_max <= 2.0f * RSPT_PI)) return fail(RSPT_E_INVALID, "disk %u: phi_max outside (0, 2 pi]", i);
-        if (k.medium_inside > d->n_media || k.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "disk %u: medium index out of range", i);
-    }
-    for (uint32_t i = 0; i < d->n_cylinders; i++) {
-        const rspt_cylinder& k = d->cylinders[i];
-        for (int j = 0; j < 16; j++)
-            if (!std::isfinite(k.object_to_world[j]) || !std::isfinite(k.world_to_object[j])) return fail(RSPT_E_INVALID, "cylinder %u: non-finite transform", i);
-        if (!std::isfinite(k.radius) || !std::isfinite(k.z_min) || !std::isfinite(k.z_max) || !std::isfinite(k.phi_max)) return fail(RSPT_E_INVALID, "cylinder %u: non-finite parameter", i);
-        if (!(k.radius > 0.0f)) return fail(RSPT_E_INVALID, "cylinder %u: radius must be positive", i);
-        if (k.z_min == k.z_max) return fail(RSPT_E_INVALID, "cylinder %u: z_min equals z_max (v divides by their difference)", i);
-        if (!(k.phi_max > 0.0f && k.phi_max <= 2.0f * RSPT_PI)) return fail(RSPT_E_INVALID, "cylinder %u: phi_max outside (0, 2 pi]", i);
-        if (k.medium_inside > d->n_media || k.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "cylinder %u: medium index out of range", i);
-    }
-    bool disk_light = false, cylinder_light = false;
-    for (uint64_t i = 0; i < d->n_prims; i++) {
-        const rspt_prim& p = d->prims[i];
-        if (p.mesh == RSPT_MESH_DISK || p.mesh == RSPT_MESH_CYLINDER) {
-            const bool dk = p.mesh == RSPT_MESH_DISK;
-            const char* kn = dk ? "disk" : "cylinder";
-            if (p.v[0] >= (dk ? d->n_disks : d->n_cylinders)) return fail(RSPT_E_INVALID, "prim %llu: %s index out of range", (unsigned long long)i, kn);
-            if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: %s's material index out of range", (unsigned long long)i, kn);
-            if (p.area_light < -1 || p.area_light >= (int64_t)d->n_lights) return fail(RSPT_E_INVALID, "prim %llu: %s's light index out of range", (unsigned long long)i, kn);
-            if (p.area_light >= 0 && (d->lights[p.area_light].kind != RSPT_LIGHT_DIFFUSE_AREA || d->lights[p.area_light].prim != i))
-                return fail(RSPT_E_INVALID, "prim %llu: %s's area light %d is not a DIFFUSE_AREA light on this primitive", (unsigned long long)i, kn, p.area_light);
-            if (p.area_light >= 0) (dk ? disk_light : cylinder_light) = true;
-            has_null |= p.material == 0xffffffffu;
-            continue;
-        }
-        if (p.mesh == RSPT_MESH_SPHERE) {
-            if (p.v[0] >= d->n_spheres) return fail(RSPT_E_INVALID, "prim %llu: sphere index out of range", (unsigned long long)i);
-            if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: material index out of range", (unsigned long long)i);
-            if (p.area_light < -1 || p.area_light >= (int64_t)d->n_lights) return fail(RSPT_E_INVALID, "prim %llu: sphere's light index out of range", (unsigned long long)i);
-            // an emissive sphere: its light is a DiffuseAreaLight on this very primitive (the pairing api.rs makes, and rspt_light.prim states)
-            if (p.area_light >= 0 && (d->lights[p.area_light].kind != RSPT_LIGHT_DIFFUSE_AREA || d->lights[p.area_light].prim != i))
-                return fail(RSPT_E_INVALID, "prim %llu: sphere's area light %d is not a DIFFUSE_AREA light on this primitive", (unsigned long long)i, p.area_light);
-            has_null |= p.material == 0xffffffffu;
-            continue;
-        }
-        if (p.mesh == RSPT_MESH_INSTANCE) {
-            if (!instanced || i >= n_top_prims || p.v[0] >= d->n_instances) return fail(RSPT_E_INVALID, "prim %llu: bad instance reference", (unsigned long long)i);
-            continue;
-        }
-        if (i >= n_top_prims && p.area_light != -1) return fail(RSPT_E_UNSUPPORTED, "prim %llu: area lights are not supported with object instancing (api.rs:2899)", (unsigned long long)i);
-        if (p.v[0] >= d->n_vertices || p.v[1] >= d->n_vertices || p.v[2] >= d->n_vertices) return fail(RSPT_E_INVALID, "prim %llu: vertex index out of range", (unsigned long long)i);
-        if (p.mesh >= d->n_meshes) return fail(RSPT_E_INVALID, "prim %llu: mesh index out of range", (unsigned long long)i);
-        if (p.material != 0xffffffffu && p.material >= d->n_materials) return fail(RSPT_E_INVALID, "prim %llu: material index out of range", (unsigned long long)i);
-        if (p.area_light >= (int64_t)d->n_lights) return fail(RSPT_E_INVALID, "prim %llu: light index out of range", (unsigned long long)i);
-        has_null |= p.material == 0xffffffffu;
-    }
-    bool any_alpha = false;
-    for (uint32_t i = 0; i < d->n_meshes; i++) {
-        const rspt_mesh& m = d->meshes[i];
-        if (m.alpha_tex > d->n_textures || m.shadow_alpha_tex > d->n_textures) return fail(RSPT_E_INVALID, "mesh %u: alpha texture index out of range", i);
-        any_alpha |= m.alpha_tex != 0 || m.shadow_alpha_tex != 0;
-        if (m.medium_inside > d->n_media || m.medium_outside > d->n_media) return fail(RSPT_E_INVALID, "mesh %u: medium index out of range", i);
-    }
-    if (d->n_media && !d->media) return fail(RSPT_E_INVALID, "null media");
-    for (uint32_t i = 0; i < d->n_media; i++) {
-        const rspt_medium& m = d->media[i];
-        if (m.kind != RSPT_MEDIUM_HOMOGENEOUS && m.kind != RSPT_MEDIUM_GRID) return fail(RSPT_E_UNSUPPORTED, "medium %u: kind %u (homogeneous and grid-density media)", i, m.kind);
-        if (m.kind == RSPT_MEDIUM_GRID) {
-            if (m.nx < 1 || m.ny < 1 || m.nz < 1 || (uint64_t)m.nx * m.ny * m.nz > (1ull << 31) || !m.density) return fail(RSPT_E_INVALID, "medium %u: bad density grid", i);
-            const float* w = m.world_to_medium;
-            if (w[12] != 0.0f || w[13] != 0.0f || w[14] != 0.0f || w[15] != 1.0f) return fail(RSPT_E_UNSUPPORTED, "medium %u: projective world_to_medium", i);
-        }
-        for (int c = 0; c < 3; c++)
-            if (!(m.sigma_a[c] >= 0.0f) || !(m.sigma_s[c] >= 0.0f) || !std::isfinite(m.sigma_a[c]) || !std::isfinite(m.sigma_s[c])) return fail(RSPT_E_INVALID, "medium %u: bad sigma_a / sigma_s", i);
-        if (!(m.g > -1.0f && m.g < 1.0f)) return fail(RSPT_E_INVALID, "medium %u: g outside (-1, 1)", i);
-    }
-    if (any_alpha)
-        for (uint64_t i = 0; i < d->n_prims; i++) {
-            const rspt_prim& p = d->prims[i];
-            if (p.mesh < d->n_meshes && p.area_light >= 0 && (d->meshes[p.mesh].alpha_tex || d->meshes[p.mesh].shadow_alpha_tex))
-                return fail(RSPT_E_UNSUPPORTED, "prim %llu: an emissive mesh with an alpha mask", (unsigned long long)i);
-        }
-    bool has_maplights = false, has_projection = false, has_goniometric = false;
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-        if (d->lights[i].kind < RSPT_LIGHT_DIFFUSE_AREA || d->lights[i].kind > RSPT_LIGHT_GONIOMETRIC) return fail(RSPT_E_UNSUPPORTED, "light %u: unsupported kind %u", i, d->lights[i].kind);
-        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->lights[i].prim >= n_top_prims || d->prims[d->lights[i].prim].mesh == RSPT_MESH_INSTANCE))   // (a sphere primitive may be named, ABI 23)
-            return fail(RSPT_E_INVALID, "light %u: prim out of range", i);
-        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && d->prims[d->lights[i].prim].mesh == RSPT_MESH_SPHERE && d->prims[d->lights[i].prim].area_light != (int32_t)i)
-            return fail(RSPT_E_INVALID, "light %u: its sphere primitive names another light", i);
-        if (d->lights[i].kind == RSPT_LIGHT_DIFFUSE_AREA && (d->prims[d->lights[i].prim].mesh == RSPT_MESH_DISK || d->prims[d->lights[i].prim].mesh == RSPT_MESH_CYLINDER) &&
-            d->prims[d->lights[i].prim].area_light != (int32_t)i)
-            return fail(RSPT_E_INVALID, "light %u: its %s primitive names another light", i, d->prims[d->lights[i].prim].mesh == RSPT_MESH_DISK ? "disk" : "cylinder");
-        if (d->lights[i].kind == RSPT_LIGHT_INFINITE && d->lights[i].prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u: envmap index out of range", i);
-        if (d->lights[i].kind == RSPT_LIGHT_PROJECTION || d->lights[i].kind == RSPT_LIGHT_GONIOMETRIC) {   // ABI 24
-            const rspt_light& l = d->lights[i];
-            const char* kn = l.kind == RSPT_LIGHT_PROJECTION ? "projection" : "goniometric";
-            const int n_par = l.kind == RSPT_LIGHT_PROJECTION ? 22 : 12;
-            for (int k = 0; k < 3; k++) if (!std::isfinite(l.L[k])) return fail(RSPT_E_INVALID, "light %u (%s): non-finite intensity", i, kn);
-            for (int k = 0; k < n_par; k++) if (!std::isfinite(l.p[k])) return fail(RSPT_E_INVALID, "light %u (%s): non-finite parameter p[%d]", i, kn, k);
-            if (l.prim != 0xffffffffu && l.prim >= d->n_envmaps) return fail(RSPT_E_INVALID, "light %u (%s): map index out of range", i, kn);
-            if (l.kind == RSPT_LIGHT_PROJECTION && (l.p[12] > l.p[14] || l.p[13] > l.p[15])) return fail(RSPT_E_INVALID, "light %u (projection): screen_bounds min above max", i);
-            has_maplights = true;
-            (l.kind == RSPT_LIGHT_PROJECTION ? has_projection : has_goniometric) = true;
-        }
-    }
-    // textures: constant / imagemap / scale; each material may bind at most RSPT_TEX_SLOTS distinct ones
-    if ((d->n_textures && !d->textures) || (d->n_images && !d->images)) return fail(RSPT_E_INVALID, "null texture / image array");
-    for (uint32_t i = 0; i < d->n_images; i++) {
-        const rspt_image& im = d->images[i];
-        auto pow2 = [](uint32_t v) { return v && !(v & (v - 1)); };
-        if (!pow2(im.width) || !pow2(im.height) || im.width > 32768 || im.height > 32768) return fail(RSPT_E_INVALID, "image %u: sides must be powers of two <= 32768 (MipMap::new resamples first)", i);
-        uint32_t nl = 1;
-        for (uint32_t m = std::max(im.width, im.height); m > 1; m >>= 1) nl++;
-        if (im.n_levels != nl || nl > 16) return fail(RSPT_E_INVALID, "image %u: n_levels %u, expected %u", i, im.n_levels, nl);
-        if (!im.texels || (im.channels != 1 && im.channels != 3)) return fail(RSPT_E_INVALID, "image %u: null texels or channels not 1 / 3", i);
-    }
-    {   // texture graph: kinds, mappings, child indices, depth (dev_texture.h evaluates at most RSPT_TEX_MAX_DEPTH levels)
-        std::vector<int> depth(d->n_textures, 0);  // 0 = not computed, -1 = on the current path (cycle)
-        std::function<int(uint32_t)> depth_of = [&](uint32_t i) -> int {
-            if (depth[i] > 0) return depth[i];
-            if (depth[i] < 0) return 1000;
-            depth[i] = -1;
-            const rspt_texture& t = d->textures[i];
-            int dmax = 0;
-            const uint32_t kids[3] = {t.tex1, t.tex2, t.tex3};
-            const int n_kids = t.kind == RSPT_TEX_MIX ? 3 : ((t.kind == RSPT_TEX_SCALE || t.kind == RSPT_TEX_CHECKERBOARD || t.kind == RSPT_TEX_DOTS) ? 2 : 0);
-            for (int k = 0; k < n_kids; k++) dmax = std::max(dmax, kids[k] < d->n_textures ? depth_of(kids[k]) : 1000);
-            return depth[i] = 1 + dmax;
-        };
-        for (uint32_t i = 0; i < d->n_textures; i++) {
-            const rspt_texture& t = d->textures[i];
-            if (t.kind < RSPT_TEX_CONSTANT || t.kind > RSPT_TEX_WRINKLED) return fail(RSPT_E_UNSUPPORTED, "texture %u: unsupported kind %u", i, t.kind);
-            const bool map2d = t.kind == RSPT_TEX_IMAGE || t.kind == RSPT_TEX_CHECKERBOARD || t.kind == RSPT_TEX_DOTS;
-            const bool map3d = t.kind == RSPT_TEX_FBM || t.kind == RSPT_TEX_MARBLE || t.kind == RSPT_TEX_WINDY || t.kind == RSPT_TEX_WRINKLED;
-            if (map2d && (t.mapping < RSPT_MAP_UV || t.mapping > RSPT_MAP_CYLINDRICAL)) return fail(RSPT_E_UNSUPPORTED, "texture %u: 2-D mapping %u", i, t.mapping);
-            if (map3d && t.mapping != RSPT_MAP_IDENTITY3D) return fail(RSPT_E_UNSUPPORTED, "texture %u: 3-D textures take the identity mapping", i);
-            if (map3d && (t.octaves < 0 || t.octaves > 64)) return fail(RSPT_E_INVALID, "texture %u: octaves out of range", i);
-            if (t.kind == RSPT_TEX_IMAGE) {
-                if (t.image >= d->n_images) return fail(RSPT_E_INVALID, "texture %u: image index out of range", i);
-                if (t.wrap > RSPT_WRAP_CLAMP) return fail(RSPT_E_INVALID, "texture %u: bad wrap mode", i);
-            }
-            const int dep = depth_of(i);
-            if (dep >= 1000) return fail(RSPT_E_INVALID, "texture %u: child index out of range or cyclic graph", i);
-            if (dep > RSPT_TEX_MAX_DEPTH) return fail(RSPT_E_UNSUPPORTED, "texture %u: graph deeper than %d levels", i, RSPT_TEX_MAX_DEPTH);
-        }
-    }
-    // materials: Material::compute_scattering_functions restated on the host (material_assembly.h), once per allow_multiple_lobes
-    std::vector<rspt_material> asm_mats[2];
-    std::vector<rspt_bxdf> asm_bx[2];
-    std::vector<rspt_mat::DynMaterial> asm_dyn[2];   // [material] when the variant has a dynamic material, else empty
-    std::vector<uint8_t> asm_is_dyn[2];
-    for (int v = 0; v < 2; v++) {
-        rspt_mat::Assembler as(d, v == 0);
-        rspt_mat::Lobes lb;
-        asm_mats[v].resize(d->n_materials);
-        asm_is_dyn[v].assign(d->n_materials, 0);
-        for (uint32_t i = 0; i < d->n_materials; i++) {
-            if (rspt_mat::Error e = as.assemble(i, &lb)) return fail(e.code, "%s", e.text.c_str());
-            lb.mat.first_bxdf = (uint32_t)asm_bx[v].size();
-            asm_mats[v][i] = lb.mat;
-            asm_bx[v].insert(asm_bx[v].end(), lb.lobes.begin(), lb.lobes.end());
-            if (lb.dynamic) {
-                if (asm_dyn[v].empty()) asm_dyn[v].resize(d->n_materials);
-                asm_dyn[v][i] = lb.dyn;
-                asm_is_dyn[v][i] = 1;
-            }
-        }
-    }
-    uint32_t shade_features = 0;
-    for (int v = 0; v < 2; v++)
-        for (const rspt_bxdf& b : asm_bx[v]) {
-            shade_features |= RSPT_SF_LOBE(b.type);
-            if (b.fresnel == RSPT_FRESNEL_CONDUCTOR) shade_features |= SF_CONDUCTOR;
-            if (b.has_sc) shade_features |= SF_SC;
-            if (b.tex_r || b.tex_t || b.tex_ax || b.tex_ay) shade_features |= SF_TEX;
-        }
-    for (int v = 0; v < 2; v++)
-        for (const rspt_material& m : asm_mats[v]) if (m.bump_tex) shade_features |= SF_TEX;
-    uint32_t shade_classes = 0;
-    {   // materials whose lobe lists have the same types in the same order (and the same textured-ness) cost a wave the same
-        std::vector<std::string> seen;
-        for (uint32_t i = 0; i < d->n_materials; i++) {
-            const rspt_material& m = asm_mats[0][i];
-            std::string sig = asm_is_dyn[0][i] ? "dyn" : "";
-            for (uint32_t l = 0; l < m.n_bxdfs; l++) {
-                const rspt_bxdf& b = asm_bx[0][m.first_bxdf + l];
-                sig += (char)('a' + b.type); sig += (char)('0' + b.fresnel); sig += (b.tex_r || b.tex_t || b.tex_ax || b.tex_ay) ? 't' : 'c';
-            }
-            if (m.bump_tex) sig += 'B';
-            if (std::find(seen.begin(), seen.end(), sig) == seen.end()) seen.push_back(sig);
-        }
-        shade_classes = (uint32_t)seen.size();
-    }
-    if (!asm_dyn[0].empty() || !asm_dyn[1].empty())  // a list built per hit may hold any lobe its material kind can push
-        shade_features |= SF_DYNAMIC | SF_TEX | 0x3feu | SF_CONDUCTOR | SF_SC;
-    for (uint32_t i = 0; i < d->n_lights; i++) {
-        const uint32_t k = d->lights[i].kind;
-        shade_features |= k == RSPT_LIGHT_DIFFUSE_AREA ? SF_L_AREA : (k == RSPT_LIGHT_POINT ? SF_L_POINT : (k == RSPT_LIGHT_SPOT ? SF_L_SPOT : (k == RSPT_LIGHT_DISTANT ? SF_L_DISTANT : (k == RSPT_LIGHT_INFINITE ? SF_L_INFINITE : SF_L_MAP))));
-    }
-    for (uint32_t i = 0; i < d->n_meshes; i++)
-        if (d->meshes[i].has_n || d->meshes[i].has_s || d->meshes[i].has_uv) shade_features |= SF_VERTEX;
-    if (instanced) shade_features |= SF_INST;
-    if (has_null || (instanced && d->instancing_mode == RSPT_INSTANCING_REFERENCE)) shade_features |= SF_NULL;
-    if (d->n_envmaps && !d->envmaps) return fail(RSPT_E_INVALID, "null envmaps");
-    for (uint32_t i = 0; i < d->n_envmaps; i++) {
-        const rspt_envmap& e = d->envmaps[i];
-        auto pow2 = [](uint32_t v) { return v && !(v & (v - 1)); };
-        if (!pow2(e.width) || !pow2(e.height) || e.width > 32768 || e.height > 32768) return fail(RSPT_E_INVALID, "envmap %u: sides must be powers of two <= 32768", i);
-        uint32_t nl = 1;
-        for (uint32_t m = std::max(e.width, e.height); m > 1; m >>= 1) nl++;
-        if (e.n_levels != nl || nl > 16) return fail(RSPT_E_INVALID, "envmap %u: n_levels %u, expected %u", i, e.n_levels, nl);
-        // ABI 24: a map that only projection / goniometric lights name carries no distribution (they never sample it); an infinite light needs its own
-        bool sampled = false, named = false;
-        for (uint32_t l = 0; l < d->n_lights; l++) {
-            if (d->lights[l].kind == RSPT_LIGHT_INFINITE && d->lights[l].prim == i) sampled = true;
-            if ((d->lights[l].kind == RSPT_LIGHT_PROJECTION || d->lights[l].kind == RSPT_LIGHT_GONIOMETRIC) && d->lights[l].prim == i) named = true;
-        }
-        const bool no_dist = !e.dist_func && e.dist_nu == 0 && e.dist_nv == 0;
-        if (!e.texels || !((named && !sampled && no_dist) || (e.dist_func && e.dist_nu != 0 && e.dist_nv != 0))) return fail(RSPT_E_INVALID, "envmap %u: null data", i);
-    }
-    // BVH: child / leaf ranges in bounds, depth <= 64 (the reference's fixed traversal stack, bvh.rs:420); with instances the
-    // object's traversal continues on the stack of the top-level one (kernels.h traverse), so the two depths add up
-    {
-        std::string err;
-        auto tree_depth = [&](uint64_t root, uint64_t node_lo, uint64_t node_hi, uint64_t prim_lo, uint64_t prim_hi) -> int {
-            std::vector<std::pair<uint32_t, uint32_t>> stack;  // node, depth
-            stack.push_back({(uint32_t)root, 1u});
-            uint64_t visited = 0;
-            uint32_t deepest = 0;
-            while (!stack.empty()) {
-                auto [ni, depth] = stack.back();
-                stack.pop_back();
-                if (++visited > node_hi - node_lo) { err = "BVH is not a tree"; return -1; }
-                deepest = std::max(deepest, depth);
-                if (depth > 64) { err = "BVH deeper than the 64-entry traversal stack"; return -2; }
-                const rspt_bvh_node& n = d->nodes[ni];
-                if (n.n_prims > 0) {
-                    if (n.offset < 0 || (uint64_t)n.offset < prim_lo || (uint64_t)n.offset + n.n_prims > prim_hi) { err = "node " + std::to_string(ni) + ": leaf range out of bounds"; return -1; }
-                } else {
-                    if (n.axis > 2 || n.offset <= (int64_t)ni || (uint64_t)n.offset >= node_hi || (uint64_t)ni + 1 >= node_hi) { err = "node " + std::to_string(ni) + ": bad children"; return -1; }
-                    stack.push_back({(uint32_t)n.offset, depth + 1});
-                    stack.push_back({ni + 1, depth + 1});
-                }
-            }
-            return (int)deepest;
-        };
-        int top_depth = 0, obj_depth = 0;
-        if (d->n_nodes) {
-            top_depth = tree_depth(0, 0, n_top_nodes, 0, n_top_prims);
-            if (top_depth < 0) return fail(top_depth == -2 ? RSPT_E_UNSUPPORTED : RSPT_E_INVALID, "%s", err.c_str());
-        }
-        for (uint32_t i = 0; instanced && i < d->n_objects; i++) {
-            const rspt_object& o = d->objects[i];
-            if (o.n_nodes == 0) continue;
-            const int dep = tree_depth(o.first_node, o.first_node, o.first_node + o.n_nodes, o.first_prim, o.first_prim + o.n_prims);
-            if (dep < 0) return fail(dep == -2 ? RSPT_E_UNSUPPORTED : RSPT_E_INVALID, "object %u: %s", i, err.c_str());
-            obj_depth = std::max(obj_depth, dep);
-        }
-        if (top_depth + obj_depth > 64) return fail(RSPT_E_UNSUPPORTED, "top-level BVH (%d levels) + object BVH (%d levels) deeper than the 64-entry traversal stack", top_depth, obj_depth);
-    }
+    // ---- everything the host refuses or prepares before the device is touched (scene_validate.h, scene_materials.h): a bad scene must not fault the GPU ----
+    SceneFacts facts;
+    SceneMaterials sm;
+    if (rspt_mat::Error e = prepare_scene(d, &facts, &sm)) return fail(e.code, "%s", e.text.c_str());
+    const bool instanced = facts.instanced, quadrics = d->n_disks || d->n_cylinders;
     HIP_TRY(hipSetDevice(g.device));
-    rspt_scene_s* s = new rspt_scene_s();
+    std::unique_ptr<rspt_scene_s> owner(new rspt_scene_s());   // an early return frees what was uploaded so far
+    rspt_scene_s* s = owner.get();
     s->dev.time_div = 1u;
-    s->has_null_material = has_null || (instanced && d->instancing_mode == RSPT_INSTANCING_REFERENCE);  // instanced hits pass through like null surfaces (Q11)
+    s->has_null_material = facts.has_null || (instanced && d->instancing_mode == RSPT_INSTANCING_REFERENCE);  // instanced hits pass through like null surfaces (Q11)
     s->has_instances = instanced;
-    s->has_alpha = any_alpha;
-    s->has_maplights = has_maplights;
-    s->maplight_kinds = has_projection ? (has_goniometric ? "projection and goniometric" : "projection") : (has_goniometric ? "goniometric" : "");
+    s->has_alpha = facts.any_alpha;
+    s->has_maplights = facts.has_maplights;
+    s->maplight_kinds = facts.has_projection ? (facts.has_goniometric ? "projection and goniometric" : "projection") : (facts.has_goniometric ? "goniometric" : "");
     s->n_materials = d->n_materials;
-    s->shade_features = shade_features;
-    s->shade_classes = shade_classes;
-    auto bail = [&](int rc) {
-        for (void* p : s->allocs) (void)hipFree(p);
-        delete s;
-        return rc;
-    };
+    s->shade_features = sm.shade_features;
+    s->shade_classes = sm.shade_classes;
+    // ---- the caller's arrays, and what scene_records.h builds from them ----
     int rc;
     const rspt_bvh_node* nodes_d = nullptr;
     const rspt_mesh* meshes_d = nullptr;
     const float* P_d = nullptr;
-    if ((rc = upload(s, d->nodes, d->n_nodes, &nodes_d))) return bail(rc);
-    const bool quadrics = d->n_disks || d->n_cylinders;
-    if (quadrics) {   // ABI 27: on the device a disk or cylinder primitive is a sphere primitive whose index names its slot behind the triangle records (dev_quadric.h: spheres, disks, cylinders)
-        std::vector<rspt_prim> pv(d->prims, d->prims + d->n_prims);
-        for (rspt_prim& p : pv) {
-            if (p.mesh == RSPT_MESH_DISK) { p.mesh = RSPT_MESH_SPHERE; p.v[0] += d->n_spheres; }
-            else if (p.mesh == RSPT_MESH_CYLINDER) { p.mesh = RSPT_MESH_SPHERE; p.v[0] += d->n_spheres + d->n_disks; }
-        }
-        if ((rc = upload(s, pv.data(), pv.size(), &s->dev.prims))) return bail(rc);
-    } else
-    if ((rc = upload(s, d->prims, d->n_prims, &s->dev.prims))) return bail(rc);
-    if ((rc = upload(s, d->meshes, d->n_meshes, &meshes_d))) return bail(rc);
+    UP(d->nodes, d->n_nodes, &nodes_d);
+    if (quadrics) UP(quadric_prims_as_sphere_slots(d), &s->dev.prims);
+    else UP(d->prims, d->n_prims, &s->dev.prims);
+    UP(d->meshes, d->n_meshes, &meshes_d);
     s->dev.meshes = meshes_d;
-    {   // media: a grid medium's density goes to the device, its record gets the device pointer and 1 / max(density) (GridDensityMedium::new, grid.rs:44-55)
-        std::vector<rspt_medium> media(d->media, d->media + d->n_media);
-        for (rspt_medium& m : media) {
-            if (m.kind != RSPT_MEDIUM_GRID) continue;
-            const size_t n = (size_t)m.nx * m.ny * m.nz;
-            float max_density = 0.0f;
-            for (size_t k = 0; k < n; k++) max_density = std::fmax(max_density, m.density[k]);   // f32::max
-            const float inv_max = 1.0f / max_density;
-            memcpy(&m.pad, &inv_max, sizeof inv_max);
-            const float* dens_d = nullptr;
-            if ((rc = upload(s, m.density, n, &dens_d))) return bail(rc);
-            m.density = dens_d;
-            s->dev.n_grid_media++;
-        }
-        if ((rc = upload(s, media.data(), media.size(), &s->dev.media))) return bail(rc);
+    if ((rc = upload_media(s, d))) return rc;
+    UP(d->P, d->n_vertices * 3, &P_d);
+    UP(d->N, d->N ? d->n_vertices * 3 : 0, &s->dev.N);
+    UP(d->S, d->S ? d->n_vertices * 3 : 0, &s->dev.S);
+    UP(d->UV, d->UV ? d->n_vertices * 2 : 0, &s->dev.UV);
+    if (wants_tri_nuv(d) && d->n_prims * 80ull <= env_size("RSPT_TRI_NUV_MAX_BYTES", (size_t)16 << 30) && env_size("RSPT_TRI_NUV", 1) != 0) {   // (skipped beyond 16 GB)
+        const float* dev_nuv = nullptr;
+        UP(pack_tri_nuv(d), &dev_nuv);
+        s->dev.tri_nuv = reinterpret_cast<const float4*>(dev_nuv);
     }
-    s->dev.n_media = d->n_media;
-    if ((rc = upload(s, d->P, d->n_vertices * 3, &P_d))) return bail(rc);
-    if ((rc = upload(s, d->N, d->N ? d->n_vertices * 3 : 0, &s->dev.N))) return bail(rc);
-    if ((rc = upload(s, d->S, d->S ? d->n_vertices * 3 : 0, &s->dev.S))) return bail(rc);
-    if ((rc = upload(s, d->UV, d->UV ? d->n_vertices * 2 : 0, &s->dev.UV))) return bail(rc);
-    {   // SceneDev::tri_nuv: every primitive's normals and uvs next to each other (80 B per primitive; skipped beyond 16 GB)
-        bool any = false;
-        for (uint32_t i = 0; i < d->n_meshes; i++) any = any || (d->meshes[i].has_n && d->N) || (d->meshes[i].has_uv && d->UV);
-        if (any && d->n_prims && d->n_prims * 80ull <= env_size("RSPT_TRI_NUV_MAX_BYTES", (size_t)16 << 30) && env_size("RSPT_TRI_NUV", 1) != 0) {
-            std::vector<float> nuv((size_t)d->n_prims * 20, 0.0f);
-            for (uint64_t i = 0; i < d->n_prims; i++) {
-                const rspt_prim& pr = d->prims[i];
-                if (pr.mesh == RSPT_MESH_INSTANCE || pr.mesh == RSPT_MESH_SPHERE || pr.mesh == RSPT_MESH_DISK || pr.mesh == RSPT_MESH_CYLINDER) continue;
-                const rspt_mesh& me = d->meshes[pr.mesh];
-                float* q = nuv.data() + 20 * i;
-                for (int k = 0; k < 3; k++) {
-                    if (me.has_n && d->N) for (int c = 0; c < 3; c++) q[3 * k + c] = d->N[3 * (size_t)pr.v[k] + c];
-                    if (me.has_uv && d->UV) for (int c = 0; c < 2; c++) q[9 + 2 * k + c] = d->UV[2 * (size_t)pr.v[k] + c];
-                }
-            }
-            const float* dev_nuv = nullptr;
-            if ((rc = upload(s, nuv.data(), nuv.size(), &dev_nuv))) return bail(rc);
-            s->dev.tri_nuv = reinterpret_cast<const float4*>(dev_nuv);
-        }
-    }
-    {   // lobes: texture ids become per-material slot numbers (1 + slot) for k_texture / k_shade
-        bool any = false;
-        for (int v = 0; v < 2; v++) {
-            std::vector<rspt_bxdf>& bx = asm_bx[v];
-            std::vector<uint32_t> slots((size_t)d->n_materials * RSPT_TEX_SLOTS, 0xffffffffu);
-            std::vector<uint8_t> mflags(d->n_materials, 0);
-            bool any_v = false;
-            for (uint32_t m = 0; m < d->n_materials; m++) {
-                const rspt_material& mat = asm_mats[v][m];
-                uint32_t* sl = slots.data() + (size_t)m * RSPT_TEX_SLOTS;
-                uint32_t n_sl = 0;
-                bool full = false;
-                auto slot_of = [&](uint32_t tex_plus_1, uint32_t flags) -> uint32_t {
-                    const uint32_t desc = (tex_plus_1 - 1u) | flags;
-                    for (uint32_t k = 0; k < n_sl; k++) if (sl[k] == desc) return k + 1u;
-                    if (n_sl == RSPT_TEX_SLOTS) { full = true; return 1u; }
-                    sl[n_sl++] = desc;
-                    return n_sl;
-                };
-                for (uint32_t l = 0; l < mat.n_bxdfs; l++) {
-                    rspt_bxdf& b = bx[mat.first_bxdf + l];
-                    const uint32_t nd = (b.remap & RSPT_LOBE_NODIFF) ? RSPT_SLOT_NODIFF : 0u;  // the m2 side of a mix (mixmat.rs:58-69)
-                    const uint32_t aflags = RSPT_SLOT_ALPHA | ((b.remap & RSPT_LOBE_REMAP) ? RSPT_SLOT_REMAP : 0u) | nd;
-                    if (b.tex_r) { b.tex_r = slot_of(b.tex_r, nd); mflags[m] |= RSPT_MAT_TEXTURED; }
-                    if (b.tex_t) { b.tex_t = slot_of(b.tex_t, nd); mflags[m] |= RSPT_MAT_TEXTURED; }
-                    if (b.tex_ax) { b.tex_ax = slot_of(b.tex_ax, aflags); mflags[m] |= RSPT_MAT_TEXTURED; }
-                    if (b.tex_ay) { b.tex_ay = slot_of(b.tex_ay, aflags); mflags[m] |= RSPT_MAT_TEXTURED; }
-                }
-                if (full) return bail(fail(RSPT_E_UNSUPPORTED, "material %u binds more than %d distinct textures", m, RSPT_TEX_SLOTS));
-                if (asm_is_dyn[v][m]) mflags[m] |= RSPT_MAT_DYNAMIC | RSPT_MAT_TEXTURED;
-                if (mat.bump_tex) mflags[m] |= RSPT_MAT_BUMP;
-                any_v |= mflags[m] != 0;
-            }
-            rspt_scene_s::MatSet& ms = s->mat_set[v];
-            ms.textured = any_v;
-            ms.dynamic = !asm_dyn[v].empty();
-            if (ms.dynamic && (rc = upload(s, asm_dyn[v].data(), asm_dyn[v].size(), &ms.dyn))) return bail(rc);
-            any |= any_v;
-            if ((rc = upload(s, asm_mats[v].data(), asm_mats[v].size(), &ms.materials)) || (rc = upload(s, bx.data(), bx.size(), &ms.bxdfs)) ||
-                (rc = upload(s, slots.data(), slots.size(), &ms.mat_slots)) || (rc = upload(s, mflags.data(), mflags.size(), &ms.mat_flags)))
-                return bail(rc);
-        }
-        s->select_materials(true);
-        if (any || any_alpha) {  // k_texture / per-path texture rows only when a material is textured; alpha masks just need the tables
-            if ((rc = upload(s, d->textures, d->n_textures, &s->tex.textures))) return bail(rc);
-            std::vector<ImageDev> imgs(d->n_images);
-            std::vector<float> pool;  // every pyramid, back to back
-            for (uint32_t i = 0; i < d->n_images; i++) {
-                const rspt_image& im = d->images[i];
-                ImageDev& o = imgs[i];
-                o.width = im.width; o.height = im.height; o.n_levels = im.n_levels; o.channels = im.channels;
-                size_t n_tex = 0;
-                for (uint32_t l = 0, w = im.width, h = im.height; l < im.n_levels; l++, w = std::max(1u, w / 2), h = std::max(1u, h / 2)) {
-                    o.level_offset[l] = (uint32_t)n_tex;
-                    n_tex += (size_t)w * h;
-                }
-                o.texel_base = pool.size();
-                s->image_base.push_back(o.texel_base);
-                pool.insert(pool.end(), im.texels, im.texels + n_tex * im.channels);
-            }
-            if ((rc = upload(s, pool.data(), pool.size(), &s->tex.texel_pool))) return bail(rc);
-            if ((rc = upload(s, imgs.data(), imgs.size(), &s->tex.images))) return bail(rc);
-            float lut[RSPT_EWA_LUT];  // MipMap::new's EWA weights (mipmap.rs:186-192), host expf like the reference's f32::exp
-            for (int i = 0; i < RSPT_EWA_LUT; i++) {
-                const float alpha = 2.0f, r2 = (float)i / (float)(RSPT_EWA_LUT - 1);
-                lut[i] = std::exp(-alpha * r2) - std::exp(-alpha);
-            }
-            if ((rc = upload(s, lut, (size_t)RSPT_EWA_LUT, &s->tex.ewa_lut))) return bail(rc);
-        }
-    }
-    if ((rc = upload(s, d->lights, d->n_lights, &s->dev.lights))) return bail(rc);
-    {   // Scene.infinite_lights (scene.rs:40-43) and their environment maps
-        std::vector<uint32_t> inf;
-        for (uint32_t i = 0; i < d->n_lights; i++)
-            if (d->lights[i].kind == RSPT_LIGHT_INFINITE) inf.push_back(i);
-        s->dev.n_infinite = (uint32_t)inf.size();
-        if ((rc = upload(s, inf.data(), inf.size(), &s->dev.infinite_lights))) return bail(rc);
-        std::vector<EnvMapDev> envs(d->n_envmaps);
-        for (uint32_t i = 0; i < d->n_envmaps; i++) {
-            const rspt_envmap& e = d->envmaps[i];
-            EnvMapDev& m = envs[i];
-            m.width = e.width; m.height = e.height; m.n_levels = e.n_levels; m.nu = e.dist_nu; m.nv = e.dist_nv;
-            size_t n_tex = 0;
-            for (uint32_t l = 0, w = e.width, h = e.height; l < e.n_levels; l++, w = std::max(1u, w / 2), h = std::max(1u, h / 2)) {
-                m.level_offset[l] = (uint32_t)n_tex;
-                n_tex += (size_t)w * h;
-            }
-            if ((rc = upload(s, e.texels, n_tex * 3, &m.texels))) return bail(rc);
-            if (!e.dist_func) continue;   // (ABI 24) the map of a projection / goniometric light: the pyramid alone, the distribution pointers stay null
-            // Distribution2D::new (sampling.rs:156-170) = Distribution1D::new (:24-49) per row and for the marginal
-            const uint32_t nu = e.dist_nu, nv = e.dist_nv;
-            std::vector<float> cdf((size_t)nv * (nu + 1)), fint(nv), mcdf(nv + 1);
-            auto dist1d = [](const float* f, uint32_t n, float* c) {
-                c[0] = 0.0f;
-                for (uint32_t k = 1; k <= n; k++) c[k] = c[k - 1] + f[k - 1] / (float)n;
-                float fi = c[n];
-                if (fi == 0.0f) for (uint32_t k = 1; k <= n; k++) c[k] = (float)k / (float)n;
-                else for (uint32_t k = 1; k <= n; k++) c[k] /= fi;
-                return fi;
-            };
-            for (uint32_t v = 0; v < nv; v++) fint[v] = dist1d(e.dist_func + (size_t)v * nu, nu, cdf.data() + (size_t)v * (nu + 1));
-            m.marg_int = dist1d(fint.data(), nv, mcdf.data());
-            if ((rc = upload(s, e.dist_func, (size_t)nu * nv, &m.cond_func)) || (rc = upload(s, cdf.data(), cdf.size(), &m.cond_cdf)) ||
-                (rc = upload(s, fint.data(), fint.size(), &m.cond_int)) || (rc = upload(s, fint.data(), fint.size(), &m.marg_func)) ||
-                (rc = upload(s, mcdf.data(), mcdf.size(), &m.marg_cdf)))
-                return bail(rc);
-        }
-        if ((rc = upload(s, envs.data(), envs.size(), &s->dev.envmaps))) return bail(rc);
-    }
+    if ((rc = upload_materials(s, d, sm))) return rc;
+    UP(d->lights, d->n_lights, &s->dev.lights);
+    if ((rc = upload_envmaps(s, d))) return rc;
     s->dev.nodes = reinterpret_cast<const float4*>(nodes_d);
     s->dev.n_nodes = (uint32_t)d->n_nodes; s->dev.n_prims = (uint32_t)d->n_prims; s->dev.n_lights = d->n_lights;
     if (d->n_nodes) {
@@ -1264,347 +974,20 @@ int rspt_scene_create(const rspt_scene_desc* d, rspt_scene_t* out) {
     } else {
         for (int i = 0; i < 3; i++) { s->dev.wb_min[i] = RSPT_FLT_MAX; s->dev.wb_max[i] = -RSPT_FLT_MAX; }  // Bounds3f::default
     }
-    // ---- four-box records (trace_w4.h): grandchildren of every interior node at even depth; with object instances every object's
-    // aggregate gets its own records behind the top-level ones, and every instance primitive the reference to the rest of its leaf ----
-    std::vector<uint32_t> obj_root(d->n_objects, RSPT_NONE), inst_cont_h(d->n_instances, RSPT_NONE);
-    if (d->n_nodes > 0) {
-        std::vector<uint2> big;
-        auto range_ref = [&](uint32_t off, uint32_t cnt) -> uint32_t {
-            if (cnt <= 15u && off <= RSPT_W4_OFFSET_MASK) return RSPT_REF_LEAF | ((cnt - 1u) << RSPT_W4_COUNT_SHIFT) | off;
-            big.push_back(make_uint2(off, cnt));
-            return RSPT_REF_LEAF | (15u << RSPT_W4_COUNT_SHIFT) | (uint32_t)(big.size() - 1);
-        };
-        auto leaf_ref = [&](uint32_t ni) -> uint32_t {
-            const rspt_bvh_node& n = d->nodes[ni];
-            if (instanced && ni < n_top_nodes)  // an instance in this leaf: the primitives behind it are reached again through its continuation reference
-                for (uint32_t i = 0; i + 1u < n.n_prims; i++) {
-                    const rspt_prim& p = d->prims[(uint32_t)n.offset + i];
-                    if (p.mesh == RSPT_MESH_INSTANCE) inst_cont_h[p.v[0]] = range_ref((uint32_t)n.offset + i + 1u, n.n_prims - i - 1u);
-                }
-            return range_ref((uint32_t)n.offset, n.n_prims);
-        };
-        // the records of the tree rooted at LinearBVHNode `root` (an interior node), depth first, with record-local indices
-        auto build_tree = [&](uint32_t root, std::vector<Wide4Node>& recs, std::vector<uint32_t>& rec_axes) {
-            const float qnan = std::numeric_limits<float>::quiet_NaN();
-            std::vector<std::pair<uint32_t, uint32_t>> todo;  // (LinearBVHNode index, record index)
-            recs.clear(); rec_axes.assign(1, 0u);
-            recs.emplace_back();
-            todo.emplace_back(root, 0u);
-            while (!todo.empty()) {
-                const auto [ai, ri] = todo.back();
-                todo.pop_back();
-                const rspt_bvh_node& a = d->nodes[ai];
-                uint32_t slot_node[4] = {RSPT_NONE, RSPT_NONE, RSPT_NONE, RSPT_NONE};
-                uint32_t axes = a.axis;
-                const uint32_t child[2] = {ai + 1u, (uint32_t)a.offset};
-                for (int gi = 0; gi < 2; gi++) {
-                    const rspt_bvh_node& c = d->nodes[child[gi]];
-                    if (c.n_prims != 0) {
-                        slot_node[2 * gi] = child[gi];
-                    } else {
-                        axes |= (uint32_t)c.axis << (2 + 2 * gi);
-                        slot_node[2 * gi] = child[gi] + 1u;
-                        slot_node[2 * gi + 1] = (uint32_t)c.offset;
-                    }
-                }
-                Wide4Node w{};
-                float lo[4][3], hi[4][3];
-                uint32_t pending[4], n_pending = 0;
-                for (int k = 0; k < 4; k++) {
-                    if (slot_node[k] == RSPT_NONE) {
-                        for (int c = 0; c < 3; c++) lo[k][c] = hi[k][c] = qnan;
-                        w.ref[k] = RSPT_NONE;
-                        continue;
-                    }
-                    const rspt_bvh_node& x = d->nodes[slot_node[k]];
-                    for (int c = 0; c < 3; c++) { lo[k][c] = x.bmin[c]; hi[k][c] = x.bmax[c]; }
-                    if (x.n_prims != 0) w.ref[k] = leaf_ref(slot_node[k]);
-                    else pending[n_pending++] = (uint32_t)k;
-                }
-                // children records are numbered so that the first slot's subtree follows its parent (pushed last)
-                for (uint32_t j = 0; j < n_pending; j++) { w.ref[pending[j]] = (uint32_t)recs.size(); recs.emplace_back(); rec_axes.push_back(0u); }
-                for (uint32_t j = n_pending; j-- > 0;) todo.emplace_back(slot_node[pending[j]], w.ref[pending[j]]);
-                for (int c = 0; c < 3; c++) {
-                    w.b[c] = make_float4(lo[0][c], lo[1][c], hi[0][c], hi[1][c]);
-                    w.b[3 + c] = make_float4(lo[2][c], lo[3][c], hi[2][c], hi[3][c]);
-                }
-                rec_axes[ri] = axes;
-                recs[ri] = w;
-            }
-        };
-        // final form of a record: child indices through `new_of` (+ base), the three axes in bits 25..26 of the first three refs (an
-        // empty slot has a NaN box, its ref is never read as a ref)
-        auto finish_rec = [&](Wide4Node w, uint32_t axes, const std::vector<uint32_t>* new_of, uint32_t base) {
-            for (int k = 0; k < 4; k++)
-                if (w.ref[k] != RSPT_NONE && !(w.ref[k] & RSPT_REF_LEAF)) w.ref[k] = (new_of ? (*new_of)[w.ref[k]] : w.ref[k]) + base;
-            for (int k = 0; k < 3; k++) w.ref[k] = (w.ref[k] & ~RSPT_W4_AXIS_MASK) | (((axes >> (2 * k)) & 3u) << RSPT_W4_AXIS_SHIFT);
-            return w;
-        };
-        std::vector<Wide4Node> recs, local;
-        std::vector<uint32_t> axes;
-        if (d->nodes[0].n_prims != 0) {
-            s->w4_root = leaf_ref(0);
-        } else {
-            build_tree(0u, local, axes);
-            // Renumber: a breadth-first prefix of RSPT_W4_TOP_MAX records goes first (k_trace_w4 keeps its first TOPCAP in LDS: any prefix of a
-            // breadth-first order is one), the others keep their depth-first order.
-            std::vector<uint32_t> new_of(local.size(), RSPT_NONE), order(1, 0u);
-            for (size_t h = 0; h < order.size() && order.size() < RSPT_W4_TOP_MAX; h++)
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t r = local[order[h]].ref[k];
-                    if (r != RSPT_NONE && !(r & RSPT_REF_LEAF) && order.size() < RSPT_W4_TOP_MAX) order.push_back(r);
-                }
-            for (size_t i = 0; i < order.size(); i++) new_of[order[i]] = (uint32_t)i;
-            uint32_t next_index = (uint32_t)order.size();
-            for (size_t i = 0; i < local.size(); i++)
-                if (new_of[i] == RSPT_NONE) new_of[i] = next_index++;
-            recs.resize(local.size());
-            for (size_t i = 0; i < local.size(); i++) recs[new_of[i]] = finish_rec(local[i], axes[i], &new_of, 0u);
-            s->w4_top = (uint32_t)order.size();
-            s->w4_root = 0u;
-        }
-        for (uint32_t o = 0; instanced && o < d->n_objects; o++) {
-            const rspt_object& ob = d->objects[o];
-            if (ob.n_nodes == 0) obj_root[o] = range_ref((uint32_t)ob.first_prim, 1u);                       // a lone primitive: no box, no aggregate
-            else if (d->nodes[ob.first_node].n_prims != 0) obj_root[o] = leaf_ref((uint32_t)ob.first_node);  // a one-leaf aggregate
-            else {
-                build_tree((uint32_t)ob.first_node, local, axes);
-                const uint32_t base = (uint32_t)recs.size();
-                for (size_t i = 0; i < local.size(); i++) recs.push_back(finish_rec(local[i], axes[i], nullptr, base));
-                obj_root[o] = base;
-            }
-        }
-        // record indices and big-leaf indices must leave bits 25..30 free; larger scenes stay on the two-box kernel
-        s->w4_ok = recs.size() <= RSPT_W4_OFFSET_MASK && big.size() <= RSPT_W4_OFFSET_MASK;
-        if (s->w4_ok && !recs.empty() && (rc = upload(s, recs.data(), recs.size(), &s->w4))) return bail(rc);
-        if (!big.empty() && (rc = upload(s, big.data(), big.size(), &s->big_leaves))) return bail(rc);
-        // ---- the quantised form of the records (trace_w4q.h) for the shadow rays of scenes without instances and alpha masks ----
-        bool any_alpha = false;
-        for (uint32_t i = 0; i < d->n_meshes; i++) any_alpha = any_alpha || d->meshes[i].alpha_tex || d->meshes[i].shadow_alpha_tex;
-        // (not for scenes with spheres either: k_trace_w4q walks triangle leaves only, and launch_trace_sph never takes it)
-        if (s->w4_ok && !recs.empty() && !instanced && !any_alpha && d->n_spheres == 0 && !quadrics && env_size("RSPT_W4Q_BUILD", 1) != 0) {
-            std::vector<Quad4Node> q(recs.size());
-            bool ok = true;
-            for (size_t i = 0; i < recs.size() && ok; i++) {
-                const Wide4Node& w = recs[i];
-                Quad4Node& o = q[i];
-                memset(&o, 0, sizeof o);
-                memcpy(o.ref, w.ref, sizeof o.ref);
-                uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0}, meta = 0;
-                for (int c = 0; c < 3 && ok; c++) {
-                    const float lo4[4] = {w.b[c].x, w.b[c].y, w.b[3 + c].x, w.b[3 + c].y}, hi4[4] = {w.b[c].z, w.b[c].w, w.b[3 + c].z, w.b[3 + c].w};
-                    double org = 0.0, top = 0.0;
-                    bool have = false;
-                    for (int k = 0; k < 4; k++) {
-                        if (lo4[k] != lo4[k]) { if (c == 0) meta |= 1u << (24 + k); continue; }   // an empty slot: a NaN box
-                        org = have ? std::min(org, (double)lo4[k]) : (double)lo4[k];
-                        top = have ? std::max(top, (double)hi4[k]) : (double)hi4[k];
-                        have = true;
-                    }
-                    if (!have) { o.org[c] = 0.0f; meta |= 100u << (8 * c); continue; }
-                    if (!std::isfinite(org) || !std::isfinite(top)) { ok = false; break; }
-                    // cell = 2^(e - 127), the smallest power of two with 255 cells covering the extent (never below 2^-67, never above 2^60)
-                    int e = 60;
-                    if (top > org) { int ex = 0; (void)std::frexp((top - org) / 255.0, &ex); e = std::max(60, std::min(187, ex + 127 - 2)); }   // (start two below the answer: the loop then takes <= 3 steps)
-                    while (e < 187 && std::ceil((top - org) / std::ldexp(1.0, e - 127)) > 255.0) e++;
-                    if (std::ceil((top - org) / std::ldexp(1.0, e - 127)) > 255.0) { ok = false; break; }
-                    const double cell = std::ldexp(1.0, e - 127);
-                    o.org[c] = (float)org;   // (org is one of the f32 planes: exact)
-                    meta |= (uint32_t)e << (8 * c);
-                    for (int k = 0; k < 4; k++) {
-                        if (lo4[k] != lo4[k]) { qlo[c] |= 255u << (8 * k); continue; }   // empty: lower plane above the upper one (and the empty bit)
-                        const double fl = std::floor(((double)lo4[k] - org) / cell), ce = std::ceil(((double)hi4[k] - org) / cell);
-                        const uint32_t a = (uint32_t)std::min(255.0, std::max(0.0, fl)), b = (uint32_t)std::min(255.0, std::max(0.0, ce));
-                        if (org + a * cell > (double)lo4[k] || org + b * cell < (double)hi4[k]) { ok = false; break; }   // outward, in exact arithmetic
-                        qlo[c] |= a << (8 * k); qhi[c] |= b << (8 * k);
-                    }
-                }
-                o.meta = meta; o.qlo[0] = qlo[0]; o.qlo[1] = qlo[1]; o.qlo[2] = qlo[2]; o.qhi_x = qhi[0]; o.qhi_y = qhi[1]; o.qhi_z = qhi[2];
-            }
-            if (ok) {
-                std::vector<float4> lb(2 * (size_t)d->n_prims, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-                for (uint64_t ni = 0; ni < d->n_nodes; ni++) {
-                    const rspt_bvh_node& n = d->nodes[ni];
-                    if (n.n_prims == 0) continue;
-                    lb[2 * (size_t)n.offset] = make_float4(n.bmin[0], n.bmin[1], n.bmin[2], n.bmax[0]);   // the layout box_hit reads (sc.nodes)
-                    lb[2 * (size_t)n.offset + 1] = make_float4(n.bmax[1], n.bmax[2], 0.0f, 0.0f);
-                }
-                if ((rc = upload(s, q.data(), q.size(), &s->w4q)) || (rc = upload(s, lb.data(), lb.size(), &s->leaf_boxes))) return bail(rc);
-            }
-        }
-    }
-    if (d->n_prims) {
-        float4* tris = nullptr;
-        // a scene with spheres keeps them behind the triangle records (dev_sphere.h SphereDev, RSPT_SPHERE_F4 float4 each)
-        const uint64_t n_slots = (uint64_t)d->n_spheres + d->n_disks + d->n_cylinders;   // (disks and cylinders take sphere slots, ABI 27)
-        hipError_t e = hipMalloc((void**)&tris, (d->n_prims * 3 + n_slots * RSPT_SPHERE_F4) * sizeof(float4));
-        if (e != hipSuccess) return bail(fail(RSPT_E_NOMEM, "triangle records: %s", hipGetErrorString(e)));
-        s->allocs.push_back(tris);
-        const uint32_t* inst_cont_d = nullptr;
-        if ((rc = upload(s, inst_cont_h.data(), inst_cont_h.size(), &inst_cont_d))) return bail(rc);
-        // alpha masks in the in-line form (dev_scene.h AlphaMask; kernels.h alpha_simple): possible when every mask of the scene is a ConstantTexture or an
-        // ImageTexture under a UVMapping2D with finite parameters, and meshes with uvs have their per-primitive copies (tri_nuv)
-        const uint32_t* mesh_mask_d = nullptr;
-        if (s->has_alpha && env_size("RSPT_ALPHA_SIMPLE", 1) != 0) {
-            std::vector<AlphaEntry> entries;
-            std::vector<uint32_t> mesh_mask(d->n_meshes, 0u);
-            std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;
-            bool simple = s->image_base.size() == d->n_images;
-            auto mask_of = [&](uint32_t tex_plus_1, AlphaMask* m) {
-                memset(m, 0, sizeof *m);
-                if (!tex_plus_1) return true;
-                const rspt_texture& tx = d->textures[tex_plus_1 - 1u];
-                if (tx.kind == RSPT_TEX_CONSTANT) { m->kind = 1u; m->value = tx.value[0]; return true; }
-                if (tx.kind != RSPT_TEX_IMAGE || tx.mapping != RSPT_MAP_UV || tx.image >= d->n_images) return false;
-                for (int k = 0; k < 4; k++) if (!std::isfinite(tx.map[k])) return false;   // (0 * su must be 0: the lookup's zero differentials)
-                const rspt_image& im = d->images[tx.image];
-                if (!im.n_levels || im.n_levels > 27u) return false;   // (level = n_levels - 1 + log2(1e-8) must be negative: mipmap.rs:236-239)
-                m->kind = 2u; m->su = tx.map[0]; m->sv = tx.map[1]; m->du = tx.map[2]; m->dv = tx.map[3];
-                m->width = im.width; m->height = im.height; m->wrap = tx.wrap; m->channels = im.channels; m->base = s->image_base[tx.image];
-                return true;
-            };
-            for (uint32_t i = 0; i < d->n_meshes && simple; i++) {
-                const rspt_mesh& me = d->meshes[i];
-                if (!me.alpha_tex && !me.shadow_alpha_tex) continue;
-                if (me.has_uv && d->UV && !s->dev.tri_nuv) { simple = false; break; }
-                const auto key = std::make_pair(me.alpha_tex, me.shadow_alpha_tex);
-                auto it = seen.find(key);
-                if (it == seen.end()) {
-                    AlphaEntry e;
-                    if (!mask_of(me.alpha_tex, &e.alpha) || !mask_of(me.shadow_alpha_tex, &e.shadow) || entries.size() >= (1u << (32 - MF_MASK_SHIFT))) { simple = false; break; }
-                    it = seen.emplace(key, (uint32_t)entries.size()).first;
-                    entries.push_back(e);
-                }
-                mesh_mask[i] = it->second;
-            }
-            if (simple && !entries.empty()) {
-                if ((rc = upload(s, entries.data(), entries.size(), &s->dev.alpha_masks)) || (rc = upload(s, mesh_mask.data(), mesh_mask.size(), &mesh_mask_d))) return bail(rc);
-                s->alpha_simple = true;
-            }
-        }
-        hipLaunchKernelGGL(k_build_tris, dim3((uint32_t)((d->n_prims + 255) / 256)), dim3(256), 0, g.stream, s->dev.prims, meshes_d, P_d, (uint32_t)d->n_prims, tris, inst_cont_d, mesh_mask_d);
-        e = hipStreamSynchronize(g.stream);
-        if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "k_build_tris: %s", hipGetErrorString(e)));
-        if (d->n_spheres) {   // ABI 23: the sphere records behind the primitive records (dev_sphere.h SphereDev; k_build_tris wrote the sphere primitives' own records)
-            std::vector<SphereDev> sph(d->n_spheres);
-            memset(sph.data(), 0, sph.size() * sizeof(SphereDev));
-            for (uint32_t k = 0; k < d->n_spheres; k++) sph[k].s = d->spheres[k];
-            e = hipMemcpy(tris + 3 * d->n_prims, sph.data(), sph.size() * sizeof(SphereDev), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "sphere records: %s", hipGetErrorString(e)));
-            s->has_spheres = true;
-            s->shade_features |= SF_SPHERE;
-            for (uint64_t i = 0; i < d->n_prims; i++)
-                if (d->prims[i].mesh == RSPT_MESH_SPHERE && d->prims[i].area_light != -1) s->has_sphere_light = true;
-        }
-        if (quadrics) {   // ABI 27: every slot again with its kind — the spheres (kind 0, as written above), then the disks, then the cylinders
-            std::vector<QuadricDev> q(n_slots);
-            memset(q.data(), 0, q.size() * sizeof(QuadricDev));
-            for (uint32_t k = 0; k < d->n_spheres; k++) { q[k].s = d->spheres[k]; q[k].kind = QK_SPHERE; }
-            for (uint32_t k = 0; k < d->n_disks; k++) { q[d->n_spheres + k].d = d->disks[k]; q[d->n_spheres + k].kind = QK_DISK; }
-            for (uint32_t k = 0; k < d->n_cylinders; k++) { q[d->n_spheres + d->n_disks + k].c = d->cylinders[k]; q[d->n_spheres + d->n_disks + k].kind = QK_CYLINDER; }
-            e = hipMemcpy(tris + 3 * d->n_prims, q.data(), q.size() * sizeof(QuadricDev), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return bail(fail(RSPT_E_HIP, "disk / cylinder records: %s", hipGetErrorString(e)));
-            s->has_spheres = s->has_quadrics = true;
-            s->has_disks = d->n_disks != 0; s->has_cylinders = d->n_cylinders != 0;
-            s->quadric_kinds = s->has_disks && s->has_cylinders ? "disk and cylinder" : (s->has_disks ? "disk" : "cylinder");
-            if (disk_light || cylinder_light) {
-                s->quadric_light_kinds = disk_light && cylinder_light ? "disk and cylinder" : (disk_light ? "disk" : "cylinder");
-                s->quadric_light_what = disk_light && cylinder_light ? "disk area lights and cylinder area lights" : (disk_light ? "disk area lights" : "cylinder area lights");
-            }
-            s->shade_features |= SF_SPHERE | SF_QUADRIC;
-        }
-        s->dev.tris = tris;
-        if (s->w4_ok && s->w4 && !instanced && (!s->has_alpha || s->alpha_simple) && env_size("RSPT_SERIAL_W4", 1) != 0) {   // the per-lane kernels' traversal (trace_serial.h)
-            s->dev.w4 = s->w4; s->dev.w4_big = s->big_leaves; s->dev.w4_root = s->w4_root;
-        }
-    }
-    if (instanced) {  // InstDev records
-        std::vector<InstDev> ins(d->n_instances);
-        std::vector<InstAnim> anims;
-        for (uint32_t i = 0; i < d->n_instances; i++) {
-            const rspt_instance& in = d->instances[i];
-            const rspt_object& o = d->objects[in.object];
-            InstDev& x = ins[i];
-            memset(&x, 0, sizeof x);
-            memcpy(x.m, in.to_world, sizeof x.m);
-            memcpy(x.mi, in.from_world, sizeof x.mi);
-            memcpy(x.m3, in.to_world + 12, sizeof x.m3);
-            memcpy(x.mi3, in.from_world + 12, sizeof x.mi3);
-            x.root_node = o.n_nodes ? (uint32_t)o.first_node : RSPT_MISS;
-            x.first_prim = (uint32_t)o.first_prim;
-            x.w4_root = obj_root[in.object];
-            bool ident = true;  // Transform::is_identity looks at m only (transform.rs:291-308)
-            for (int r = 0; r < 4; r++)
-                for (int c = 0; c < 4; c++) ident &= in.to_world[4 * r + c] == (r == c ? 1.0f : 0.0f);
-            x.identity = ident ? 1u : 0u;
-            x.anim = RSPT_MISS;
-            if (in.animated) {   // a moving instance (ABI 20): AnimatedTransform::new's decomposition of the two keys, as for a moving camera
-                if (!std::isfinite(in.time[0]) || !std::isfinite(in.time[1]) || !(in.time[1] > in.time[0]))
-                    return bail(fail(RSPT_E_INVALID, "instance %u: animated with time[1] <= time[0] or a non-finite key time", i));
-                for (int k = 0; k < 16; k++)
-                    if (!std::isfinite(in.to_world_end[k]) || !std::isfinite(in.from_world_end[k]))
-                        return bail(fail(RSPT_E_INVALID, "instance %u: non-finite end key matrix", i));
-                // transform_point divides by the homogeneous weight and the reference asserts it is not zero (transform.rs:505): an end key whose
-                // rows 3 are all zero can only produce such weights
-                if (in.to_world_end[12] == 0.0f && in.to_world_end[13] == 0.0f && in.to_world_end[14] == 0.0f && in.to_world_end[15] == 0.0f)
-                    return bail(fail(RSPT_E_INVALID, "instance %u: end key with a zero homogeneous row", i));
-                if (in.from_world_end[12] == 0.0f && in.from_world_end[13] == 0.0f && in.from_world_end[14] == 0.0f && in.from_world_end[15] == 0.0f)
-                    return bail(fail(RSPT_E_INVALID, "instance %u: end key inverse with a zero homogeneous row", i));
-                InstAnim an;
-                memset(&an, 0, sizeof an);
-                if (camanim::camera_keys(in.to_world, in.time[0], in.to_world_end, in.time[1], &an.keys)) {   // false: equal keys = not actually animated
-                    memcpy(an.mi_end, in.from_world_end, sizeof an.mi_end);
-                    bool ie = true;
-                    for (int r = 0; r < 4; r++)
-                        for (int c = 0; c < 4; c++) ie &= in.to_world_end[4 * r + c] == (r == c ? 1.0f : 0.0f);
-                    an.identity_end = ie ? 1u : 0u;
-                    x.anim = (uint32_t)anims.size();
-                    anims.push_back(an);
-                }
-            }
-        }
-        if (!anims.empty()) {
-            if (s->has_alpha && !s->w4_ok) return bail(fail(RSPT_E_UNSUPPORTED, "moving object instances together with alpha-masked meshes in a scene whose records outgrow the four-box kernel"));
-            if ((rc = upload(s, anims.data(), anims.size(), &s->dev.inst_anim))) return bail(rc);
-            s->has_animated = true;
-            s->shade_features |= SF_ANIM;
-        }
-        if ((rc = upload(s, ins.data(), ins.size(), &s->dev.inst))) return bail(rc);
-        s->dev.n_inst = d->n_instances;
-        s->dev.inst_fixed = d->instancing_mode == RSPT_INSTANCING_FIXED ? 1u : 0u;
-    }
-    if (d->n_nodes > 1 && !instanced) {  // pair records: both children's boxes next to each other (trace_wide.h)
-        std::vector<uint32_t> pair_of(d->n_nodes, 0u);
-        uint32_t n_pairs = 0;
-        for (uint64_t i = 0; i < d->n_nodes; i++)
-            if (d->nodes[i].n_prims == 0) pair_of[i] = n_pairs++;
-        std::vector<PairNode> pairs(n_pairs);
-        for (uint64_t i = 0; i < d->n_nodes; i++) {
-            const rspt_bvh_node& n = d->nodes[i];
-            if (n.n_prims != 0) continue;
-            const uint32_t ci[2] = {(uint32_t)i + 1u, (uint32_t)n.offset};
-            const rspt_bvh_node& a = d->nodes[ci[0]];
-            const rspt_bvh_node& b = d->nodes[ci[1]];
-            PairNode& p = pairs[pair_of[i]];
-            p.q0 = make_float4(a.bmin[0], b.bmin[0], a.bmax[0], b.bmax[0]);
-            p.q1 = make_float4(a.bmin[1], b.bmin[1], a.bmax[1], b.bmax[1]);
-            p.q2 = make_float4(a.bmin[2], b.bmin[2], a.bmax[2], b.bmax[2]);
-            p.c0 = a.n_prims ? (ci[0] | RSPT_REF_LEAF) : pair_of[ci[0]];
-            p.c1 = b.n_prims ? (ci[1] | RSPT_REF_LEAF) : pair_of[ci[1]];
-            p.self = (uint32_t)i;
-            p.axis = n.axis;
-        }
-        if ((rc = upload(s, pairs.data(), pairs.size(), &s->pairs))) return bail(rc);
-    }
-    *out = s;
+    const W4Records w4 = build_w4(d, facts);
+    if ((rc = upload_w4(s, d, facts, w4))) return rc;
+    if (d->n_prims && (rc = build_primitive_records(s, d, facts, w4, meshes_d, P_d))) return rc;
+    if (instanced && (rc = upload_instances(s, d, w4))) return rc;
+    if (d->n_nodes > 1 && !instanced) UP(build_pairs(d), &s->pairs);
+    *out = owner.release();
     return RSPT_OK;
 }
+#undef UP
 
 int rspt_scene_destroy(rspt_scene_t s) {
     if (!s) return RSPT_OK;
     if (g.inited) { (void)hipSetDevice(g.device); (void)hipStreamSynchronize(g.stream); }
-    for (void* p : s->allocs) (void)hipFree(p);
-    delete s;
+    delete s;   // (its destructor frees the device arrays)
     return RSPT_OK;
 }
 

@@ -46,7 +46,7 @@ struct Wide4Node {      // 128 B, 128-byte aligned
 #define RSPT_W4_LDS 12       // stack entries per lane (8 B each) kept in LDS: 24 KB per workgroup
 #endif
 #ifndef RSPT_W4_TOP
-#define RSPT_W4_TOP 56       // records nearest the root (a breadth-first prefix, numbered first by rspt_scene_create) that every
+#define RSPT_W4_TOP 56       // records nearest the root (a breadth-first prefix, numbered first by scene_records.h build_w4) that every
                              // workgroup keeps in LDS: their fetches leave the L1 request path that bounds the kernel.
                              // 2048 * RSPT_W4_LDS + 112 * RSPT_W4_TOP must stay under ~31 KB or only four workgroups fit a CU
                              // (measured C2 / C3 Msamples/s: (16, 0) 366 / 1139; (12, 56) 379 / 1172; (11, 72) 382 / 1161;
@@ -54,7 +54,7 @@ struct Wide4Node {      // 128 B, 128-byte aligned
                              //  six waves per SIMD forced with amdgpu_waves_per_eu (80 VGPRs, 13 spilled) and (10, 56): 366 / 1141)
 #endif
 static_assert(2048 * RSPT_W4_LDS + 112 * RSPT_W4_TOP <= 64 * 1024, "k_trace_w4 LDS budget (64 KB per workgroup)");
-#define RSPT_W4_TOP_MAX 512  // the breadth-first prefix rspt_scene_create numbers first: the largest TOPCAP any instantiation keeps in LDS
+#define RSPT_W4_TOP_MAX 512  // the breadth-first prefix scene_records.h build_w4 numbers first: the largest TOPCAP any instantiation keeps in LDS
 #ifndef RSPT_W4_SHAPE_DEFAULT
 #define RSPT_W4_SHAPE_DEFAULT 0
 #endif

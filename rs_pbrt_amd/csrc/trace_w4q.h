@@ -20,7 +20,7 @@
 
 namespace rspt {
 
-struct Quad4Node {      // 64 B, 64-byte aligned: the four boxes of a Wide4Node on an 8-bit grid (rspt_scene_create quantises, outward)
+struct Quad4Node {      // 64 B, 64-byte aligned: the four boxes of a Wide4Node on an 8-bit grid (scene_records.h quantise_w4, outward)
     float org[3];       // the frame's origin: plane = org + q * 2^(e - 127)
     uint32_t meta;      // e_x | e_y << 8 | e_z << 16 (biased exponents of the cell sizes) | empty-slot mask << 24
     uint32_t qlo[3];    // per axis: the four slots' lower planes, slot k in byte k
