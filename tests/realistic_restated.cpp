@@ -466,6 +466,15 @@ int real_trace_from_film(const rspt_lens_element* elements, uint32_t n, const fl
     out[0] = r.o.x; out[1] = r.o.y; out[2] = r.o.z; out[3] = r.d.x; out[4] = r.d.y; out[5] = r.d.z; out[6] = r.t_max;
     return 1;
 }
+// trace_lenses_from_scene, the same way
+int real_trace_from_scene(const rspt_lens_element* elements, uint32_t n, const float o[3], const float d[3], float out[7]) {
+    orc::real::Camera cam;
+    cam.el.assign(elements, elements + n);
+    orc::Ray r = orc::real::default_ray();
+    if (!orc::real::trace_lenses_from_scene(cam, orc::Ray{orc::V3{o[0], o[1], o[2]}, orc::V3{d[0], d[1], d[2]}, orc::INF, 0.0f}, &r)) return 0;
+    out[0] = r.o.x; out[1] = r.o.y; out[2] = r.o.z; out[3] = r.d.x; out[4] = r.d.y; out[5] = r.d.z; out[6] = r.t_max;
+    return 1;
+}
 // compute_thick_lens_approximation over an element table and a film diagonal in metres: pz[2], fz[2]; 0 or the failing assertion
 int real_cardinal_points(const rspt_lens_element* elements, uint32_t n, float film_diagonal, float pz[2], float fz[2]) {
     orc::real::Camera cam;

@@ -41,6 +41,7 @@ def build_realistic_restated(with_li=None):
     L.real_rays.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.real_setup.argtypes = [vp, u32, f, f, f, u32, vp, vp, C.c_int]
     L.real_trace_from_film.argtypes = [vp, u32, vp, vp, vp]
+    L.real_trace_from_scene.argtypes = [vp, u32, vp, vp, vp]
     L.real_cardinal_points.argtypes = [vp, u32, f, vp, vp]
     L.real_t_neg_count.restype = C.c_uint64
     L.real_sample.restype = None
