@@ -612,6 +612,29 @@ typedef struct {
 /* version of this header the library was built against */
 int rspt_abi_version(void);
 
+/* The shade-math mode (additive to ABI 27: no struct changes, a caller finds the two symbols or does not).  Process-wide, host-only state: the calls need no
+ * device and work before rspt_init and before any scene exists.
+ *   RSPT_SHADE_MATH_EXACT (the default): every kernel computes what rs_pbrt's Rust computes, operation by operation: correctly rounded f32 division and
+ *       square root, the host libm's sinf / cosf / logf / log2f / expf / acosf / atan2f restated.  Renders are held to the reference bit for bit.
+ *   RSPT_SHADE_MATH_FAST: rspt_render (and its siblings) under RSPT_INTEGRATOR_PATH with the Sobol' or Halton sampler launches fast-math builds of the
+ *       triangle shade sets (diffuse, plastic, textured, their -halton forms, generic): f32 division and square root by the hardware's reciprocal /
+ *       square-root instructions (1 ulp) and the device's native or library sin / cos / log / log2 / exp / acos / atan2.  Nothing is reassociated or
+ *       contracted, denormal handling stays.  The generic set's fast build keeps the correctly rounded division and square root (only its functions
+ *       change): with the approximate ones it did not hold the tolerance below on a bump-mapped scene.
+ *   What fast never changes: traversal and hit records, the samplers with their sample indices and dimensions, the queues, the texture stage, camera
+ *       rays, the film with its filter weights (the film's w channel is bit-identical to an exact render's), the light tables.
+ *   Tolerance fast is held to: a camera sample deviates when a channel differs from the exact value by more than
+ *       1e-3 * max(1, |exact|); at most 1e-3 of a render's samples may deviate (a roulette draw or an edge hit decided the other way changes a whole
+ *       path), and the film's RMSE against the exact film stays below 1e-3.
+ *   Renders fast does not cover run the exact kernels, bit for bit, and that is not an error: the ao, directlighting, volpath and whitted integrators, the
+ *       pixel samplers, and scenes that need the dynamic, moving, sphere, quadric or map-light shade sets.
+ * rspt_set_shade_math: a value above RSPT_SHADE_MATH_FAST is RSPT_E_INVALID (the text names shade_math) and leaves the mode as it was.
+ * The environment variable RSPT_SHADE_MATH = exact | fast, when set and non-empty, overrides the call for every render of the process (rspt_get_shade_math
+ * keeps answering what the call set); any other value makes rspt_render answer RSPT_E_INVALID naming RSPT_SHADE_MATH. */
+enum { RSPT_SHADE_MATH_EXACT = 0, RSPT_SHADE_MATH_FAST = 1 };
+int rspt_set_shade_math(uint32_t mode);
+uint32_t rspt_get_shade_math(void);
+
 /* Select the HIP device (ordinal among visible devices) and create streams.
  * Must be called once per process before any other call. */
 int rspt_init(int32_t device);

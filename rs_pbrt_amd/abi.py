@@ -20,6 +20,7 @@ INTEGRATOR_PATH, INTEGRATOR_AO, INTEGRATOR_DIRECT, INTEGRATOR_VOLPATH, INTEGRATO
 MEDIUM_HOMOGENEOUS, MEDIUM_GRID = 1, 2
 DIRECT_SAMPLE_ALL, DIRECT_SAMPLE_ONE = 0, 1
 LIGHTS_UNIFORM, LIGHTS_POWER, LIGHTS_SPATIAL = 0, 1, 2
+SHADE_MATH_EXACT, SHADE_MATH_FAST = 0, 1      # rspt_set_shade_math (additive to ABI 27): the default bit parity | fast-math builds of the triangle shade sets
 CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT, CAMERA_REALISTIC = 0, 1, 2, 3      # rspt_render_desc.camera_kind (0 = what a zero-filled desc always meant); 3: ABI 26
 MAX_LENS_ELEMENTS = 32
 TEX_CONSTANT, TEX_IMAGE, TEX_SCALE, TEX_MIX, TEX_CHECKERBOARD, TEX_DOTS, TEX_FBM, TEX_MARBLE, TEX_WINDY, TEX_WRINKLED = range(1, 11)

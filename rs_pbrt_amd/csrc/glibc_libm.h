@@ -21,6 +21,35 @@
 #include <math.h>
 #include <stdint.h>
 
+// RSPT_FAST_MATH (defined by the tu_shade_f*.hip units alone, before their includes): in DEVICE code each rspt_*f below is the hardware / OCML
+// form instead of the restatement: v_sin_f32 / v_cos_f32 / v_log_f32 / v_exp_f32 behind __sinf / __cosf / __logf / __log2f / __expf, OCML's acosf / atanf / atan2f
+// where the hardware has no native form.  Every function here is __device__-only and a unit's device code is a code object of its own, so no exact unit
+// and no host code sees a fast body; the host pass of a fast unit parses the restatement as every other unit does.  One switch per function, so that a
+// function whose substitution costs too much accuracy can be put back alone.
+#if defined(RSPT_FAST_MATH) && defined(__HIP_DEVICE_COMPILE__)
+#define RSPT_FAST_DEFAULT 1
+#else
+#define RSPT_FAST_DEFAULT 0
+#endif
+#ifndef RSPT_FAST_SINCOS   /* (-DRSPT_FAST_<FN>=0 on a fast unit's command line keeps that function exact there: how a substitution is tried alone) */
+#define RSPT_FAST_SINCOS RSPT_FAST_DEFAULT
+#endif
+#ifndef RSPT_FAST_LOG
+#define RSPT_FAST_LOG RSPT_FAST_DEFAULT
+#endif
+#ifndef RSPT_FAST_LOG2
+#define RSPT_FAST_LOG2 RSPT_FAST_DEFAULT
+#endif
+#ifndef RSPT_FAST_EXP
+#define RSPT_FAST_EXP RSPT_FAST_DEFAULT
+#endif
+#ifndef RSPT_FAST_ACOS
+#define RSPT_FAST_ACOS RSPT_FAST_DEFAULT
+#endif
+#ifndef RSPT_FAST_ATAN
+#define RSPT_FAST_ATAN RSPT_FAST_DEFAULT
+#endif
+
 // ---- sinf / cosf as glibc computes them -------------------------------------------------------------------------------------
 // Rust's f32::sin / f32::cos are the host libm's sinf / cosf.  glibc (2.28 and later) evaluates them in double precision: argument
 // reduction by n = round(x * 2 / pi) (a scaled float-to-int conversion), a degree-7 sine or degree-8 cosine polynomial in the reduced
@@ -62,8 +91,13 @@ GL_FN float glibc_sincosf(float y, int cosine) {
     }
     return cosine ? cosf(y) : sinf(y);
 }
+#if RSPT_FAST_SINCOS
+GL_FN float rspt_sinf(float y) { return __sinf(y); }
+GL_FN float rspt_cosf(float y) { return __cosf(y); }
+#else
 GL_FN float rspt_sinf(float y) { return glibc_sincosf(y, 0); }
 GL_FN float rspt_cosf(float y) { return glibc_sincosf(y, 1); }
+#endif
 
 // ---- logf / log2f / expf / acosf / atan2f as glibc 2.35 computes them ------------------------------------------------------------
 // Same idea as sinf / cosf above.  logf, log2f, expf: ARM optimized-routines algorithms in double precision with libm's own tables
@@ -74,6 +108,9 @@ GL_FN float rspt_cosf(float y) { return glibc_sincosf(y, 1); }
 GL_TABLE double GLIBC_LOGF_TAB[32] = {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2, 0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2, 0x1.49539f0f010b0p+0, -0x1.01eae7f513a67p-2, 0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3, 0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3, 0x1.25e227b0b8ea0p+0, -0x1.1aa2bc79c8100p-3, 0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4, 0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4, 0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5, 0x1.0000000000000p+0, 0x0.0p+0, 0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5, 0x1.ca4b31f026aa0p-1, 0x1.c5e53aa362eb4p-4, 0x1.b2036576afce6p-1, 0x1.526e57720db08p-3, 0x1.9c2d163a1aa2dp-1, 0x1.bc2860d224770p-3, 0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2, 0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2};
 GL_TABLE double GLIBC_LOG2F_TAB[32] = {0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2, 0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2, 0x1.49539f0f010b0p+0, -0x1.7418b0a1fb77bp-2, 0x1.3c995b0b80385p+0, -0x1.39de91a6dcf7bp-2, 0x1.30d190c8864a5p+0, -0x1.01d9bf3f2b631p-2, 0x1.25e227b0b8ea0p+0, -0x1.97c1d1b3b7af0p-3, 0x1.1bb4a4a1a343fp+0, -0x1.2f9e393af3c9fp-3, 0x1.12358f08ae5bap+0, -0x1.960cbbf788d5cp-4, 0x1.0953f419900a7p+0, -0x1.a6f9db6475fcep-5, 0x1.0000000000000p+0, 0x0.0p+0, 0x1.e608cfd9a47acp-1, 0x1.338ca9f24f53dp-4, 0x1.ca4b31f026aa0p-1, 0x1.476a9543891bap-3, 0x1.b2036576afce6p-1, 0x1.e840b4ac4e4d2p-3, 0x1.9c2d163a1aa2dp-1, 0x1.40645f0c6651cp-2, 0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2, 0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2};
 GL_TABLE uint64_t GLIBC_EXP2F_TAB[32] = {0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull, 0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull, 0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull, 0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, 0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull, 0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+#if RSPT_FAST_LOG
+GL_FN float rspt_logf(float x) { return __logf(x); }
+#else
 GL_FN_COLD float rspt_logf(float x) {
     uint32_t ix = GL_F2U(x);
     if (ix == 0x3f800000u) return 0.0f;
@@ -98,6 +135,10 @@ GL_FN_COLD float rspt_logf(float x) {
     y = fma(y, r2, y0 + r);
     return (float)y;
 }
+#endif
+#if RSPT_FAST_LOG2
+GL_FN float rspt_log2f(float x) { return __log2f(x); }
+#else
 GL_FN float rspt_log2f(float x) {
     uint32_t ix = GL_F2U(x);
     if (ix == 0x3f800000u) return 0.0f;
@@ -124,6 +165,10 @@ GL_FN float rspt_log2f(float x) {
     y = fma(y, r2, p);
     return (float)y;
 }
+#endif
+#if RSPT_FAST_EXP
+GL_FN float rspt_expf(float x) { return __expf(x); }
+#else
 GL_FN_COLD float rspt_expf(float x) {
     const double xd = (double)x;
     const uint32_t abstop = (GL_F2U(x) >> 20) & 0x7ffu;
@@ -148,6 +193,10 @@ GL_FN_COLD float rspt_expf(float x) {
     y = y * s;
     return (float)y;
 }
+#endif
+#if RSPT_FAST_ACOS
+GL_FN float rspt_acosf(float x) { return ::acosf(x); }
+#else
 GL_FN_COLD float rspt_acosf(float x) {  // e_acosf.c
     const float one = 1.0f, pi = 3.1415925026e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f, pS0 = 1.6666667163e-01f, pS1 = -3.2556581497e-01f,
                 pS2 = 2.0121252537e-01f, pS3 = -4.0055535734e-02f, pS4 = 7.9153501429e-04f, pS5 = 3.4793309169e-05f, qS1 = -2.4033949375e+00f, qS2 = 2.0209457874e+00f,
@@ -183,6 +232,11 @@ GL_FN_COLD float rspt_acosf(float x) {  // e_acosf.c
         return 2.0f * (df + w);
     }
 }
+#endif
+#if RSPT_FAST_ATAN
+GL_FN float rspt_atanf(float x) { return ::atanf(x); }
+GL_FN float rspt_atan2f(float y, float x) { return ::atan2f(y, x); }
+#else
 GL_FN_COLD float rspt_atanf(float x) {  // s_atanf.c
     const float hi0 = 4.6364760399e-01f, hi1 = 7.8539812565e-01f, hi2 = 9.8279368877e-01f, hi3 = 1.5707962513e+00f;   // atanhi / atanlo: atan(0.5), atan(1), atan(1.5), atan(inf)
     const float lo0 = 5.0121582440e-09f, lo1 = 3.7748947079e-08f, lo2 = 3.4473217170e-08f, lo3 = 7.5497894159e-08f;
@@ -241,4 +295,4 @@ GL_FN_COLD float rspt_atan2f(float y, float x) {  // e_atan2f.c
     if (m == 2) return pi - (z - pi_lo);
     return (z - pi_lo) - pi;
 }
-
+#endif

@@ -1380,6 +1380,36 @@ __global__ __launch_bounds__(256) void k_shade_m(RSPT_SHADE_ARGS) {
     __shared__ ShadeStage stage;
     RSPT_SHADE_CALL(true, &stage);
 }
+// The fast-math builds (rspt_set_shade_math): the same four bodies under names of their own, so that the mangled name of every instantiation
+// above stays what it was.  They are instantiated only in the tu_shade_f*.hip units, which define RSPT_FAST_MATH (glibc_libm.h: the device's native sin / cos / log /
+// exp) and are compiled without correctly rounded f32 division and square root (csrc/Makefile); each unit's device code is its own code object, so an exact
+// unit never picks up a fast body.  Same launch bounds, same LDS as the twins.
+template <uint32_t F>
+__global__ __launch_bounds__(256) void k_shade_fast(RSPT_SHADE_ARGS) {
+    extern __shared__ uint32_t sob_tab[];
+    __shared__ uint32_t s_wave[4][5], s_base[4];
+    RSPT_SHADE_CALL(false, nullptr);
+}
+template <uint32_t F, int W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) void k_shade_fast_w(RSPT_SHADE_ARGS) {
+    extern __shared__ uint32_t sob_tab[];
+    __shared__ uint32_t s_wave[4][5], s_base[4];
+    RSPT_SHADE_CALL(false, nullptr);
+}
+template <uint32_t F, int W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) void k_shade_fast_mw(RSPT_SHADE_ARGS) {
+    extern __shared__ uint32_t sob_tab[];
+    __shared__ uint32_t s_wave[4][5], s_base[4];
+    __shared__ ShadeStage stage;
+    RSPT_SHADE_CALL(true, &stage);
+}
+template <uint32_t F>
+__global__ __launch_bounds__(256) void k_shade_fast_m(RSPT_SHADE_ARGS) {
+    extern __shared__ uint32_t sob_tab[];
+    __shared__ uint32_t s_wave[4][5], s_base[4];
+    __shared__ ShadeStage stage;
+    RSPT_SHADE_CALL(true, &stage);
+}
 // MOVE: after the last iteration of a batch, whatever is still in the queue (paths cut by RSPT_NULL_PASSES; normally nothing) hands its radiance to the film
 // moved = 0: no MOVE launch has run in this batch (max_depth below RSPT_MOVE_FROM): every slot's radiance is still in L_eta by slot, copied over as a whole
 RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_move_flush(PathBuf pb, const uint32_t* __restrict__ q_active, const QueueCounts* __restrict__ cnt, uint32_t qcap, uint32_t moved) {

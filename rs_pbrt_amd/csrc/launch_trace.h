@@ -256,6 +256,17 @@ void launch_trace(uint32_t grid, const rspt_scene_s* s, const TraceCall& c) {
     static void (*const variants[2][2])(uint32_t, const rspt_scene_s*, const TraceCall&, uint32_t*) = {{launch_trace_v<ANY, OUT_MODE, false, false>, launch_trace_v<ANY, OUT_MODE, false, true>}, {launch_trace_v<ANY, OUT_MODE, true, false>, launch_trace_v<ANY, OUT_MODE, true, true>}};
     variants[s->has_instances][s->has_alpha](grid, s, c, xcur);
 }
+// ---- the shade-math mode (include/rspt.h rspt_set_shade_math): host-only, process-wide ----
+std::atomic<uint32_t> g_shade_math{RSPT_SHADE_MATH_EXACT};
+// the mode a render runs under: RSPT_SHADE_MATH = exact | fast when set and non-empty (how an unmodified caller reaches the mode), else what rspt_set_shade_math
+// left; -1: the variable holds something else
+int shade_math_mode() {
+    const char* e = getenv("RSPT_SHADE_MATH");
+    if (!e || !*e) return (int)g_shade_math.load();
+    if (!strcmp(e, "exact")) return RSPT_SHADE_MATH_EXACT;
+    if (!strcmp(e, "fast")) return RSPT_SHADE_MATH_FAST;
+    return -1;
+}
 // ---- the shade stage's instantiations (kernels.h k_shade<F>) ----
 // A scene is served by the narrowest compiled feature set that covers what it can put in front of the stage (rspt_scene_s.shade_features
 // + the sampler): the code for every other lobe type, light kind, texture slot, instance transform and the Halton sampler folds away,
@@ -266,16 +277,24 @@ typedef void (*ShadeKernel)(RSPT_SHADE_ARGS);
 // VGPRs is spilled); dflt = which of the three runs.  Measured on one box (profiles/r03_ab_shade.md; Msamples/s of C2 / the C3 stand-in,
 // k_shade seconds per step): generic 212 VGPRs 423 / 1685 (0.161 / 0.578 s); diffuse 158 VGPRs = 3 waves as compiled 459 (0.111 s), forced to
 // 4 waves 455; plastic 173 VGPRs as compiled 1749 (0.531 s), 168 + 24 B of spills = 3 waves 1841 (0.470 s), 128 + 152 B = 4 waves 1791.
-struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */ };
+struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */
+                      ShadeKernel f_natural, f_w3, f_w4, f_move; /* the fast-math builds of the same four (kernels.h k_shade_fast*, tu_shade_f*.hip); nullptr: the set has none */ };
 const ShadeVariant g_shade_variants[] = {
-    {SV_DIFFUSE, "diffuse", k_shade<SV_DIFFUSE>, k_shade_w<SV_DIFFUSE, 3>, k_shade_w<SV_DIFFUSE, 4>, 3, k_shade_mw<SV_DIFFUSE, 3>},   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
+    {SV_DIFFUSE, "diffuse", k_shade<SV_DIFFUSE>, k_shade_w<SV_DIFFUSE, 3>, k_shade_w<SV_DIFFUSE, 4>, 3, k_shade_mw<SV_DIFFUSE, 3>,
+     k_shade_fast<SV_DIFFUSE>, k_shade_fast_w<SV_DIFFUSE, 3>, k_shade_fast_w<SV_DIFFUSE, 4>, k_shade_fast_mw<SV_DIFFUSE, 3>},   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
                                                                                                            //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
-    {SV_PLASTIC, "plastic", k_shade<SV_PLASTIC>, k_shade_w<SV_PLASTIC, 3>, k_shade_w<SV_PLASTIC, 4>, 3, k_shade_mw<SV_PLASTIC, 3>},
-    {SV_TEXTURED, "textured", k_shade<SV_TEXTURED>, k_shade_w<SV_TEXTURED, 3>, k_shade_w<SV_TEXTURED, 4>, 0, k_shade_m<SV_TEXTURED>},
-    {SV_DIFFUSE_H, "diffuse-halton", k_shade<SV_DIFFUSE_H>, k_shade_w<SV_DIFFUSE_H, 3>, k_shade_w<SV_DIFFUSE_H, 3>, 3, k_shade_mw<SV_DIFFUSE_H, 3>},   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
-    {SV_PLASTIC_H, "plastic-halton", k_shade<SV_PLASTIC_H>, k_shade_w<SV_PLASTIC_H, 3>, k_shade_w<SV_PLASTIC_H, 3>, 3, k_shade_mw<SV_PLASTIC_H, 3>},
-    {SV_TEXTURED_H, "textured-halton", k_shade<SV_TEXTURED_H>, k_shade_w<SV_TEXTURED_H, 3>, k_shade_w<SV_TEXTURED_H, 3>, 3, k_shade_mw<SV_TEXTURED_H, 3>},   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
-    {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>},
+    {SV_PLASTIC, "plastic", k_shade<SV_PLASTIC>, k_shade_w<SV_PLASTIC, 3>, k_shade_w<SV_PLASTIC, 4>, 3, k_shade_mw<SV_PLASTIC, 3>,
+     k_shade_fast<SV_PLASTIC>, k_shade_fast_w<SV_PLASTIC, 3>, k_shade_fast_w<SV_PLASTIC, 4>, k_shade_fast_mw<SV_PLASTIC, 3>},
+    {SV_TEXTURED, "textured", k_shade<SV_TEXTURED>, k_shade_w<SV_TEXTURED, 3>, k_shade_w<SV_TEXTURED, 4>, 0, k_shade_m<SV_TEXTURED>,
+     k_shade_fast<SV_TEXTURED>, k_shade_fast_w<SV_TEXTURED, 3>, k_shade_fast_w<SV_TEXTURED, 4>, k_shade_fast_m<SV_TEXTURED>},
+    {SV_DIFFUSE_H, "diffuse-halton", k_shade<SV_DIFFUSE_H>, k_shade_w<SV_DIFFUSE_H, 3>, k_shade_w<SV_DIFFUSE_H, 3>, 3, k_shade_mw<SV_DIFFUSE_H, 3>,
+     k_shade_fast<SV_DIFFUSE_H>, k_shade_fast_w<SV_DIFFUSE_H, 3>, k_shade_fast_w<SV_DIFFUSE_H, 3>, k_shade_fast_mw<SV_DIFFUSE_H, 3>},   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
+    {SV_PLASTIC_H, "plastic-halton", k_shade<SV_PLASTIC_H>, k_shade_w<SV_PLASTIC_H, 3>, k_shade_w<SV_PLASTIC_H, 3>, 3, k_shade_mw<SV_PLASTIC_H, 3>,
+     k_shade_fast<SV_PLASTIC_H>, k_shade_fast_w<SV_PLASTIC_H, 3>, k_shade_fast_w<SV_PLASTIC_H, 3>, k_shade_fast_mw<SV_PLASTIC_H, 3>},
+    {SV_TEXTURED_H, "textured-halton", k_shade<SV_TEXTURED_H>, k_shade_w<SV_TEXTURED_H, 3>, k_shade_w<SV_TEXTURED_H, 3>, 3, k_shade_mw<SV_TEXTURED_H, 3>,
+     k_shade_fast<SV_TEXTURED_H>, k_shade_fast_w<SV_TEXTURED_H, 3>, k_shade_fast_w<SV_TEXTURED_H, 3>, k_shade_fast_mw<SV_TEXTURED_H, 3>},   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
+    {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>,
+     k_shade_fast<SV_GENERIC>, k_shade_fast_w<SV_GENERIC, 3>, k_shade_fast_w<SV_GENERIC, 4>, k_shade_fast_m<SV_GENERIC>},
     {SV_DYNAMIC, "dynamic", k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, 0, nullptr},   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
     {SF_ALL, "moving", k_shade<SF_ALL>, k_shade<SF_ALL>, k_shade<SF_ALL>, 0, nullptr},                     // + moving object instances (dev_scene.h inst_at)
     // scenes with analytic spheres (SF_SPHERE; Sobol' and Halton): the generic / dynamic sets with the sphere arm (dev_bsdf.h shade_sph).  Only
@@ -297,9 +316,12 @@ const ShadeVariant g_shade_variants[] = {
 };
 // RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
 // move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)
-ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr) {
+// fast (rspt_set_shade_math / RSPT_SHADE_MATH, resolved by the caller): the fast-math builds of the chosen set, picked by the same switches, where the set has them;
+// *fast_out then says so.  A set without them (dynamic, moving, sphere, quadric, map-light) is served by its exact kernels: a mode that permits approximation may be exact.
+ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr, bool fast = false, bool* fast_out = nullptr) {
     const char* force = getenv("RSPT_SHADE_VARIANT");
     if (move_out) *move_out = nullptr;
+    if (fast_out) *fast_out = false;
     const bool sph = (need & SF_SPHERE) != 0, ml = (need & SF_L_MAP) != 0, quad = (need & SF_QUADRIC) != 0;
     for (const ShadeVariant& v : g_shade_variants) {
         if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
@@ -309,7 +331,10 @@ ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* 
         if (force && *force && strcmp(force, v.name) != 0 && (v.features | SF_DYNAMIC | SF_ANIM) != SF_ALL) continue;
         if (name_out) *name_out = v.name;
         const size_t waves = env_size("RSPT_SHADE_WAVES", (size_t)v.dflt);
-        if (move_out && waves == (size_t)v.dflt) *move_out = v.move;
+        const bool f = fast && v.f_natural != nullptr;
+        if (fast_out) *fast_out = f;
+        if (move_out && waves == (size_t)v.dflt) *move_out = f ? v.f_move : v.move;
+        if (f) return waves == 3 ? v.f_w3 : (waves == 4 ? v.f_w4 : v.f_natural);
         return waves == 3 ? v.w3 : (waves == 4 ? v.w4 : v.natural);
     }
     if (sph || ml) return nullptr;   // (not reached: the dynamic sphere set covers every sphere scene, which never holds moving instances)

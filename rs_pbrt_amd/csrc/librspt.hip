@@ -749,6 +749,13 @@ int upload_instances(rspt_scene_s* s, const rspt_scene_desc* d, const scene::W4R
 extern "C" {
 
 int rspt_abi_version(void) { return RSPT_ABI_VERSION; }
+// the shade-math mode: host-only state, no device needed (launch_trace.h g_shade_math; render_run.h picks the kernels)
+int rspt_set_shade_math(uint32_t mode) {
+    if (mode > RSPT_SHADE_MATH_FAST) return fail(RSPT_E_INVALID, "shade_math %u (0 exact, 1 fast)", mode);
+    g_shade_math.store(mode);
+    return RSPT_OK;
+}
+uint32_t rspt_get_shade_math(void) { return g_shade_math.load(); }
 // Replaces: BVHAccel::new (bvh.rs:96-392), on the device; see bvh_device.h
 int64_t rspt_bvh_build_gpu(const float* P, uint64_t n_vertices, const uint32_t* tri_idx, uint64_t n_tris, uint32_t max_prims_in_node,
                            rspt_bvh_node* nodes_out, uint64_t nodes_cap, uint32_t* ordered_out) {

@@ -29,6 +29,7 @@ struct RenderRun {
     uint32_t ns = 1, ao_n = 1, dl_levels = 0, dl_H = 1, dl_R = 1, move_first = 1;
     bool counters = false, ao = false, dl_lane = false, dl_one_round = false, move = false;
     const char* shade_name = "generic"; ShadeKernel shade_k = nullptr, shade_move_k = nullptr;
+    int shade_math = RSPT_SHADE_MATH_EXACT; bool shade_fast = false; char shade_name_fast[48];   // validate(): the mode; size_batches(): whether fast builds serve this render (then shade_name = "<set>-fast")
     // prepare(): the per-lane directlighting forms' arrays, iteration counts, launch geometry, events (kev: per-launch durations, each pair recorded on the
     // stream its kernel runs on — closest-hit, shadow-ray, shade [+ texture])
     float4* dl_tex = nullptr; int32_t* dl_nls = nullptr; uint32_t* dl_words = nullptr; rspt_mat::Built* dl_dyn = nullptr;
@@ -88,6 +89,7 @@ int upload_lens(const rspt_render_desc* d, LensSystem* L) {
 int RenderRun::validate() {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !d) return fail(RSPT_E_INVALID, "null scene or render desc");
+    if ((shade_math = shade_math_mode()) < 0) return fail(RSPT_E_INVALID, "RSPT_SHADE_MATH=%s (exact or fast)", getenv("RSPT_SHADE_MATH"));
     if (int rc = validate_camera(d)) return rc;
     // ABI 26: the realistic camera is served where k_raygen_lens and the per-sample ray weight are: path and ao in the wavefront form (Sobol' / Halton).  The
     // schedules of volpath, directlighting and whitted consume k_raygen's output in their own ways and the pixel samplers' per-tile walk makes its own camera
@@ -429,7 +431,11 @@ int RenderRun::size_batches() {
     if (pixel_sampler) cap = std::max<size_t>(n_blocks, 1024);   // one path slot per tile (tile_serial.h); the samples' results have their own arrays
     // round 6: the path integrator's MOVING path state (kernels.h PathBuf::move) — wherever the scene's shade instantiation has a MOVE form; not with moving instances
     // (their ray times are kept by original slot) and not under the pixel samplers / the other integrators, which keep slots for life.  RSPT_MOVE=0: slots, as before.
-    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k);
+    // the fast-math builds (rspt_set_shade_math): the path integrator's wavefront form under Sobol' / Halton only, and only the sets that have them; every other render
+    // of a fast-mode process runs the exact kernels under the plain name
+    const bool want_fast = shade_math == RSPT_SHADE_MATH_FAST && d->integrator == RSPT_INTEGRATOR_PATH && !pixel_sampler;
+    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k, want_fast, &shade_fast);
+    if (shade_k && shade_fast) { snprintf(shade_name_fast, sizeof shade_name_fast, "%s-fast", shade_name); shade_name = shade_name_fast; }
     if (!shade_k) return fail(RSPT_E_UNSUPPORTED, s->has_maplights ? "RSPT_SHADE_VARIANT names no instantiation with the projection / goniometric arms (generic-maplight, all-maplight)"
                                                                   : s->has_quadrics ? "RSPT_SHADE_VARIANT names no instantiation with the disk / cylinder arm (generic-quadric, dynamic-quadric)"
                                                                   : "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");

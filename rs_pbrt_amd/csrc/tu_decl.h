@@ -186,6 +186,38 @@ RSPT_TU_SHADE_M(SV_GENERIC)
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_MH)
 RSPT_TU_SHADE_MW(SV_DIFFUSE_H, 3) RSPT_TU_SHADE_MW(SV_PLASTIC_H, 3)
 #endif
+// ---- the fast-math builds of the triangle sets (kernels.h k_shade_fast*; rspt_set_shade_math) ----
+// One group per exact group above (SHADE_C: the generic set only), each in a unit of its own, tu_shade_f*.hip, which defines RSPT_FAST_MATH and is compiled without
+// correctly rounded f32 division / square root (csrc/Makefile).  The dynamic, moving, sphere, quadric and map-light sets have no fast build.
+#define RSPT_TU_FSHADE(F) RSPT_TU_X template __global__ void k_shade_fast<F>(RSPT_SHADE_ARGS);
+#define RSPT_TU_FSHADE_W(F, W) RSPT_TU_X template __global__ void k_shade_fast_w<F, W>(RSPT_SHADE_ARGS);
+#define RSPT_TU_FSHADE_M(F) RSPT_TU_X template __global__ void k_shade_fast_m<F>(RSPT_SHADE_ARGS);
+#define RSPT_TU_FSHADE_MW(F, W) RSPT_TU_X template __global__ void k_shade_fast_mw<F, W>(RSPT_SHADE_ARGS);
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FA)
+RSPT_TU_FSHADE(SV_DIFFUSE) RSPT_TU_FSHADE_W(SV_DIFFUSE, 3) RSPT_TU_FSHADE_W(SV_DIFFUSE, 4)
+RSPT_TU_FSHADE(SV_PLASTIC) RSPT_TU_FSHADE_W(SV_PLASTIC, 3) RSPT_TU_FSHADE_W(SV_PLASTIC, 4)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FB)
+RSPT_TU_FSHADE(SV_TEXTURED) RSPT_TU_FSHADE_W(SV_TEXTURED, 3) RSPT_TU_FSHADE_W(SV_TEXTURED, 4)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FC)
+RSPT_TU_FSHADE(SV_GENERIC) RSPT_TU_FSHADE_W(SV_GENERIC, 3) RSPT_TU_FSHADE_W(SV_GENERIC, 4)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FH)
+RSPT_TU_FSHADE(SV_DIFFUSE_H) RSPT_TU_FSHADE_W(SV_DIFFUSE_H, 3) RSPT_TU_FSHADE(SV_PLASTIC_H) RSPT_TU_FSHADE_W(SV_PLASTIC_H, 3) RSPT_TU_FSHADE(SV_TEXTURED_H) RSPT_TU_FSHADE_W(SV_TEXTURED_H, 3)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FMA)
+RSPT_TU_FSHADE_MW(SV_DIFFUSE, 3) RSPT_TU_FSHADE_MW(SV_PLASTIC, 3) RSPT_TU_FSHADE_M(SV_DIFFUSE) RSPT_TU_FSHADE_M(SV_PLASTIC)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FMB)
+RSPT_TU_FSHADE_M(SV_TEXTURED) RSPT_TU_FSHADE_MW(SV_TEXTURED_H, 3)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FMC)
+RSPT_TU_FSHADE_M(SV_GENERIC)
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_FMH)
+RSPT_TU_FSHADE_MW(SV_DIFFUSE_H, 3) RSPT_TU_FSHADE_MW(SV_PLASTIC_H, 3)
+#endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_W4Q)
 RSPT_TU_X template __global__ void k_trace_w4q<0>(SceneDev, const Quad4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, uint32_t*, rspt_hit*, uint32_t*, int, int, uint32_t, uint32_t, const float4*);
 RSPT_TU_X template __global__ void k_trace_w4q<1>(SceneDev, const Quad4Node*, const uint2*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, const rspt_ray*, uint32_t*, rspt_hit*, uint32_t*, int, int, uint32_t, uint32_t, const float4*);

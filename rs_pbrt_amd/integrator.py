@@ -36,11 +36,16 @@ class Film:
 
 
 class PathIntegrator:
-    def __init__(self, max_depth=5, camera=None, sampler=None, pixel_bounds=None, rr_threshold=1.0, light_sample_strategy="spatial"):
+    def __init__(self, max_depth=5, camera=None, sampler=None, pixel_bounds=None, rr_threshold=1.0, light_sample_strategy="spatial", shade_math=None):
         """camera: an rspt_render_desc carrying camera + film + sampler parameters
         (scenes.make_render_desc); sampler / pixel_bounds are accepted for signature parity:
         the sampler is the Sobol' sampler configured in the desc, pixel_bounds equal the film's
-        sample bounds (the reference ignores the "pixelbounds" parameter too, api.rs:288-304)."""
+        sample bounds (the reference ignores the "pixelbounds" parameter too, api.rs:288-304).
+        shade_math: None (leave the process-wide mode, lib.set_shade_math, as it is), "exact" or "fast": the mode render() runs under; it puts the
+        previous mode back afterwards.  No counterpart in the reference."""
+        if shade_math is not None and shade_math not in lib.SHADE_MATH:
+            raise ValueError("shade_math must be None, 'exact' or 'fast'")
+        self.shade_math = shade_math
         if camera is None:
             raise ValueError("Unable to create camera")  # api.rs:467-483 panics the same way
         if light_sample_strategy not in _STRATEGIES:
@@ -67,9 +72,14 @@ class PathIntegrator:
         rd = self._desc(shard)
         own = not isinstance(scene, lib.DeviceScene)
         ds = lib.DeviceScene(scene) if own else scene
+        before = lib.get_shade_math() if self.shade_math is not None else None
         try:
+            if before is not None:
+                lib.set_shade_math(self.shade_math)
             pixels, self.stats = lib.render(ds, rd)
         finally:
+            if before is not None:
+                lib.set_shade_math(before)
             if own:
                 ds.close()
         film = Film(rd)

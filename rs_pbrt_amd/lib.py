@@ -17,7 +17,7 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
            "rspt_dev_upload", "rspt_dev_download", "rspt_last_error", "rspt_last_counters", "rspt_bvh_build", "rspt_bvh_last_error",
            "rspt_bvh_build_gpu", "rspt_bvh_build_bounds", "rspt_comm_unique_id", "rspt_comm_init", "rspt_comm_destroy", "rspt_light_distribution", "rspt_libm",
            "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library", "rspt_realistic_camera_setup",
-           "rspt_camera_rays", "rspt_quadric_intersect")
+           "rspt_camera_rays", "rspt_quadric_intersect", "rspt_set_shade_math", "rspt_get_shade_math")
 
 
 def tree_source_hash():
@@ -91,6 +91,8 @@ def lib():
         L.rspt_comm_library.restype = C.c_char_p
         L.rspt_comm_unique_id.argtypes = [vp]
         L.rspt_comm_init.argtypes = [i32, i32, vp]
+        L.rspt_set_shade_math.argtypes = [u32]
+        L.rspt_get_shade_math.restype = u32
         _LIB = L
     return _LIB
 
@@ -101,6 +103,19 @@ def _check(rc):
 
 
 MATERIAL_DYNAMIC = 1000
+
+SHADE_MATH = {"exact": abi.SHADE_MATH_EXACT, "fast": abi.SHADE_MATH_FAST}
+
+
+def set_shade_math(mode):
+    """rspt_set_shade_math: "exact" (the default: bit parity with the reference) or "fast" (fast-math builds of the triangle shade sets under the path integrator
+    with the sobol / halton samplers; include/rspt.h says what changes and the tolerance).  Process-wide, host only; an integer is passed through as it is."""
+    _check(lib().rspt_set_shade_math(SHADE_MATH[mode] if isinstance(mode, str) else int(mode)))
+
+
+def get_shade_math():
+    """"exact" or "fast": what set_shade_math last set (the environment's RSPT_SHADE_MATH, which overrides it per render, is not reflected)"""
+    return {v: k for k, v in SHADE_MATH.items()}[int(lib().rspt_get_shade_math())]
 
 
 def camera_decompose(rd):

@@ -15,6 +15,8 @@ pub const RSPT_MESH_SPHERE: u32 = 0xffff_fffe;   // ABI 23: v[0] = index into sp
 pub const RSPT_MESH_DISK: u32 = 0xffff_fffd;     // ABI 27: v[0] = index into disks
 pub const RSPT_MESH_CYLINDER: u32 = 0xffff_fffc; // ABI 27: v[0] = index into cylinders
 pub const RSPT_NO_MATERIAL: u32 = 0xffff_ffff;
+pub const RSPT_SHADE_MATH_EXACT: u32 = 0;   // rspt_set_shade_math (additive to ABI 27): the default, bit parity
+pub const RSPT_SHADE_MATH_FAST: u32 = 1;    // fast-math builds of the triangle shade sets under path + sobol / halton
 
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct RsptBvhNode { pub bmin: [f32; 3], pub bmax: [f32; 3], pub offset: i32, pub n_prims: u16, pub axis: u8, pub pad: u8 } // 32 B
@@ -105,6 +107,8 @@ pub enum RsptSceneOpaque {}
 #[link(name = "rspt")]
 extern "C" {
     pub fn rspt_abi_version() -> c_int;
+    pub fn rspt_set_shade_math(mode: u32) -> c_int;                                // process-wide, host only; the environment's RSPT_SHADE_MATH=exact|fast overrides it
+    pub fn rspt_get_shade_math() -> u32;
     pub fn rspt_init(device: i32) -> c_int;
     pub fn rspt_shutdown();
     pub fn rspt_scene_create(desc: *const RsptSceneDesc, out: *mut *mut RsptSceneOpaque) -> c_int;

@@ -18,8 +18,13 @@ KEYS = (("vgprs", r" VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("sgprs", r"Tot
         ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("waves", r"Occupancy \[waves/SIMD\]: (\d+)"))
 
 
+FAST_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-Xarch_device", "-fapprox-func"]   # csrc/Makefile FAST_FLAGS: the fast-math shade units, tu_shade_f*.hip
+
+
 def remarks(tu):
-    r = subprocess.run([HIPCC] + FLAGS + [os.path.basename(tu)], cwd=os.path.dirname(tu), stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, errors="replace")
+    name = os.path.basename(tu)
+    fast = FAST_FLAGS if name.startswith("tu_shade_f") and name not in ("tu_shade_fc.hip", "tu_shade_fmc.hip") else []   # (the generic set keeps exact division)
+    r = subprocess.run([HIPCC] + FLAGS + fast + [os.path.basename(tu)], cwd=os.path.dirname(tu), stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, errors="replace")
     if r.returncode != 0:
         sys.exit("%s failed on %s:\n%s" % (HIPCC, tu, r.stderr[-2000:]))
     return r.stderr
