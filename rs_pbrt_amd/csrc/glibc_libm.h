@@ -21,7 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
-// RSPT_FAST_MATH (defined by the tu_shade_f*.hip units alone, before their includes): in DEVICE code each rspt_*f below is the hardware / OCML
+// RSPT_FAST_MATH (defined for the SHADE_F* groups of tu.hip alone, on the command line and so before every include): in DEVICE code each rspt_*f below is the hardware / OCML
 // form instead of the restatement: v_sin_f32 / v_cos_f32 / v_log_f32 / v_exp_f32 behind __sinf / __cosf / __logf / __log2f / __expf, OCML's acosf / atanf / atan2f
 // where the hardware has no native form.  Every function here is __device__-only and a unit's device code is a code object of its own, so no exact unit
 // and no host code sees a fast body; the host pass of a fast unit parses the restatement as every other unit does.  One switch per function, so that a

@@ -563,11 +563,12 @@ RDEV TraceResult traverse(const SceneDev& sc, const TexTables& tt, f3 o, f3 d, f
 // out_mode 0: float4 (prim, b0, b1, b2) into hit_cont/hit_mis by slot; 1: rspt_hit AoS by queue
 // position (stage hook); ANY: occluded[slot] (mode 0) or rspt_hit.prim (mode 1).
 // out_inst (INST, closest hit, continuation rays only): 0 or 1 + instance of the hit, by slot
+#define RSPT_TRACE_ARGS                                                                                                                                           \
+    SceneDev sc, TexTables tt, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, const rspt_ray* __restrict__ rays_a, \
+        const rspt_ray* __restrict__ rays_b, float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,                               \
+        rspt_hit* __restrict__ out_hits, unsigned long long* __restrict__ counters, uint32_t* __restrict__ out_inst
 template <bool ANY, int OUT_MODE, bool COUNT, bool INST, bool ALPHA, bool ANIM = false>
-__global__ __launch_bounds__(RSPT_TRACE_BLOCK) void k_trace(SceneDev sc, TexTables tt, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr,
-                                                            uint32_t count_imm, const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                            float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,
-                                                            rspt_hit* __restrict__ out_hits, unsigned long long* __restrict__ counters, uint32_t* __restrict__ out_inst) {
+__global__ __launch_bounds__(RSPT_TRACE_BLOCK) void k_trace(RSPT_TRACE_ARGS) {
     __shared__ uint32_t stack[RSPT_LDS_STACK * RSPT_TRACE_BLOCK];
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     const uint32_t stride = gridDim.x * RSPT_TRACE_BLOCK;
@@ -1381,7 +1382,7 @@ __global__ __launch_bounds__(256) void k_shade_m(RSPT_SHADE_ARGS) {
     RSPT_SHADE_CALL(true, &stage);
 }
 // The fast-math builds (rspt_set_shade_math): the same four bodies under names of their own, so that the mangled name of every instantiation
-// above stays what it was.  They are instantiated only in the tu_shade_f*.hip units, which define RSPT_FAST_MATH (glibc_libm.h: the device's native sin / cos / log /
+// above stays what it was.  They are instantiated only in the SHADE_F* groups of tu.hip, which are compiled with RSPT_FAST_MATH (glibc_libm.h: the device's native sin / cos / log /
 // exp) and are compiled without correctly rounded f32 division and square root (csrc/Makefile); each unit's device code is its own code object, so an exact
 // unit never picks up a fast body.  Same launch bounds, same LDS as the twins.
 template <uint32_t F>

@@ -72,8 +72,9 @@ struct LaneDesc {
 // k_raygen has left the camera ray, the sample's index and film position in slot i
 // ANIM (round 6): moving instances — the sample's ray time is what k_raygen left in pb.time[i]
 // WH: WhittedIntegrator::li (DlSerial<.., WH>; the host passes n_arr = 0: whitted.rs requests no sample arrays)
+#define RSPT_LANE_ARGS SceneDev sc, TexTables tt, LightDistDev ld, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list, LaneDesc ln
 template <bool INST, bool ALPHA, bool ANIM = false, bool WH = false>
-__global__ __launch_bounds__(64) void k_lane_dl(SceneDev sc, TexTables tt, LightDistDev ld, RenderDev rd, Batch bt, PathBuf pb, const uint32_t* __restrict__ pix_list, LaneDesc ln) {
+__global__ __launch_bounds__(64) void k_lane_dl(RSPT_LANE_ARGS) {
     __shared__ uint32_t stack[RSPT_LDS_STACK * 64];
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= bt.n) return;

@@ -93,6 +93,23 @@ uint32_t bundle_blocks_per_cu() {
     }
     return (uint32_t)blocks;
 }
+// One launch of a four-box kernel (k_trace_w4 / k_trace_w4quad: RSPT_W4_ARGS), of a packet kernel (RSPT_PK_ARGS) and of k_trace_fixup (RSPT_FIXUP_ARGS): a call
+// site names what differs between the sites, the rest is the call's and its TracePre's.  (QueueCounts layout: the overflow word sits two after its cursor)
+template <typename K>
+void launch_w4(K kern, uint32_t grid, uint32_t block, size_t lds, const rspt_scene_s* s, const TraceCall& c, const TracePre& p, int leaf, uint32_t spill_rows, uint32_t* hi, uint32_t* xcur,
+               uint32_t chunk) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, p.stream, s->dev, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.occ,
+                       c.hits, c.cursor + 2, p.ovf, p.spill, spill_rows, p.refill, leaf, s->w4_top, hi, xcur, chunk);
+}
+template <typename K>
+void launch_pk(K kern, uint32_t grid, const rspt_scene_s* s, const TraceCall& c, const TracePre& p, uint32_t chunk) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RSPT_PW_BLOCK), 0, p.stream, s->dev, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.hits,
+                       chunk, s->leaf_boxes);
+}
+template <typename K>
+void launch_fixup(K kern, uint32_t grid, const rspt_scene_s* s, const TraceCall& c, const TracePre& p, uint32_t* hi) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, s->dev, s->tex, c.cursor + 2, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+}
 template <bool ANY, int OUT_MODE, bool INST, bool ALPHA>
 void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur) {
     const SceneDev& sc = s->dev;
@@ -108,12 +125,15 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
     const bool anim_w4 = s->has_animated && s->w4_ok && which >= 2 && env_size("RSPT_ANIM_W4", 1) != 0 && env_size("RSPT_INSTANCE_KERNEL", 1) != 0;   // (round 6: the reference-order loop serves moving instances next to masks too, so every A/B switch stays bit-exact)
     const bool slow = c.count || which == 0 || (s->has_animated && !anim_w4) || (special && (!s->w4_ok || env_size("RSPT_INSTANCE_KERNEL", 1) == 0));
     if (slow) {
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+        };
         if (INST && s->has_animated)   // moving instances (alone or next to alpha-masked meshes): the reference-order loop with the interpolation (its own instantiations; no node / triangle counters)
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+            go(k_trace<ANY, OUT_MODE, false, true, ALPHA, true>);
         else if (c.count)
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, true, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+            go(k_trace<ANY, OUT_MODE, true, INST, ALPHA>);
         else
-            hipLaunchKernelGGL((k_trace<ANY, OUT_MODE, false, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, c.queue, c.count_ptr, c.count_imm, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, c.counters, hi);
+            go(k_trace<ANY, OUT_MODE, false, INST, ALPHA>);
         return;
     }
     const uint32_t pw_chunk = p.chunk | (env_size("RSPT_PW_ADAPT", 1) != 0 ? 0u : 1u);   // (bit 0: the kernels do not shrink the claim on short queues — trace_w4.h)
@@ -124,13 +144,10 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
         if (anim_w4) {   // moving instances; next to alpha-masked meshes the masks in line (ALPHA = 2) where every mask allows it, else through alpha_pass
             // RSPT_PW_ENTER: lanes in front of an instance wait until that many of a wave do (trace_w4.h, the entry phase); it rides in bits 8.. of the leaf threshold
             const int pw_enter = (int)std::min<size_t>(std::max<size_t>(env_size("RSPT_PW_ENTER", RSPT_PW_ENTER), 1), 64);
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                                   c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, (p.leaf & 0xff) | (pw_enter << 8), s->w4_top, hi, xcur, pw_chunk);
-            };
+            auto go = [&](auto kern) { launch_w4(kern, p.pgrid, RSPT_PW_BLOCK, 0, s, c, p, (p.leaf & 0xff) | (pw_enter << 8), spill_rows, hi, xcur, pw_chunk); };
             if constexpr (ALPHA) { if (s->alpha_simple) go(k_trace_w4<ANY, OUT_MODE, true, 2, true>); else go(k_trace_w4<ANY, OUT_MODE, true, 1, true>); }
             else go(k_trace_w4<ANY, OUT_MODE, true, 0, true>);
-            hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, true, ALPHA, true>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+            launch_fixup(k_trace_fixup<ANY, OUT_MODE, true, ALPHA, true>, grid, s, c, p, hi);
             return;
         }
     }
@@ -160,10 +177,7 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
         if (pk >= 3 && camera_packet_ok(s, which, xcur)) {
             // RSPT_CAMERA_PACKET=3 / 4: the frustum walk once per bundle of two / four packets (trace_bundle.h: with 128 / 256 or more samples per pixel a bundle is one pixel), same
             // arguments, same records; the grid is what the kernel's registers allow
-            auto go = [&](auto kern, uint32_t per_cu) {
-                hipLaunchKernelGGL(kern, dim3(hinted_grid(c.queue_hint, grid_for(per_cu), RSPT_PW_BLOCK)), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr,
-                                   c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.hits, pw_chunk, s->leaf_boxes);
-            };
+            auto go = [&](auto kern, uint32_t per_cu) { launch_pk(kern, hinted_grid(c.queue_hint, grid_for(per_cu), RSPT_PW_BLOCK), s, c, p, pw_chunk); };
             if (pk == 3) go(k_trace_w4pb<OUT_MODE, 2>, bundle_blocks_per_cu<OUT_MODE, 2>());
             else go(k_trace_w4pb<OUT_MODE, 4>, bundle_blocks_per_cu<OUT_MODE, 4>());
             return;
@@ -172,8 +186,7 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
             // (no spill rows and 6 KB of LDS: its grid is its own — six workgroups per CU = the six waves per SIMD its 79 VGPRs allow; RSPT_PK_BLOCKS_PER_CU for A/B builds)
             const uint32_t kgrid = hinted_grid(c.queue_hint, grid_for((uint32_t)std::min<size_t>(std::max<size_t>(env_size("RSPT_PK_BLOCKS_PER_CU", 6), 1), 8)), RSPT_PW_BLOCK);
             // RSPT_CAMERA_PACKET=2: the packet walk with one frustum test per record instead of the per-ray slot tests (trace_frustum.h), same arguments, same records
-            hipLaunchKernelGGL(pk == 2 ? k_trace_w4pf<OUT_MODE> : k_trace_w4pk<OUT_MODE>, dim3(kgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm,
-                               c.cursor, c.ra, c.rb, c.oa, c.ob, c.hits, pw_chunk, s->leaf_boxes);
+            launch_pk(pk == 2 ? k_trace_w4pf<OUT_MODE> : k_trace_w4pk<OUT_MODE>, kgrid, s, c, p, pw_chunk);
             return;
         }
     }
@@ -191,30 +204,25 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
                 if (!done) { bad = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess; (void)hipGetLastError(); done = true; }
                 if (bad) return false;   // the device refuses that much dynamic LDS: the default shape serves the launch
                 const uint32_t bgrid = hinted_grid(c.queue_hint, grid_for(per_cu), block);
-                hipLaunchKernelGGL(kern, dim3(bgrid), dim3(block), lds, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                                   c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+                launch_w4(kern, bgrid, block, lds, s, c, p, p.leaf, spill_rows, hi, xcur, pw_chunk);
                 return true;
             };
             const bool launched = shape == 1 ? go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 1024, 512>, 1024u, 512u, 1u) : go(k_trace_w4<ANY, OUT_MODE, false, 0, false, 512, 256>, 512u, 256u, 2u);
             if (launched) {
-                if (trace_can_overflow(s))
-                    hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+                if (trace_can_overflow(s)) launch_fixup(k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>, grid, s, c, p, hi);
                 return;
             }
         }
     }
     if (ALPHA && s->alpha_simple)   // every mask of the scene is evaluated in line (kernels.h alpha_simple): the traversal keeps its register budget
-        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 2 : 0>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+        launch_w4(k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 2 : 0>, p.pgrid, RSPT_PW_BLOCK, 0, s, c, p, p.leaf, spill_rows, hi, xcur, pw_chunk);
     else if (special || (which >= 2 && s->w4_ok))
-        hipLaunchKernelGGL((k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 1 : 0>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, spill_rows, p.refill, p.leaf, s->w4_top, hi, xcur, pw_chunk);
+        launch_w4(k_trace_w4<ANY, OUT_MODE, INST, ALPHA ? 1 : 0>, p.pgrid, RSPT_PW_BLOCK, 0, s, c, p, p.leaf, spill_rows, hi, xcur, pw_chunk);
     else
         hipLaunchKernelGGL((k_trace_pw<ANY, OUT_MODE>), dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->pairs, c.queue, c.count_ptr, c.count_imm, c.cursor, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf,
                            p.refill, p.leaf);
     // with every spill row in use the plain four-box kernel cannot overflow (RSPT_W4_MAX_STACK): no second pass to launch
-    if (trace_can_overflow(s))
-        hipLaunchKernelGGL((k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>), dim3(grid), dim3(RSPT_TRACE_BLOCK), 0, p.stream, sc, s->tex, n_overflow, p.ovf, c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, hi);
+    if (trace_can_overflow(s)) launch_fixup(k_trace_fixup<ANY, OUT_MODE, INST, ALPHA>, grid, s, c, p, hi);
 }
 // Scenes with spheres (ABI 23): k_trace_w4<.., SPH = true> with every spill row (a non-instanced four-box walk cannot then overflow, so no
 // k_trace_fixup — whose reference-order loop has no sphere test); no node counters, no quantised shadow-ray records (k_trace_w4q walks triangle
@@ -224,13 +232,8 @@ void launch_trace_v(uint32_t grid, const rspt_scene_s* s, const TraceCall& c, ui
 // rspt_render check w4_ok first; rspt_render refuses RSPT_COUNTERS on sphere scenes.
 template <bool ANY, int OUT_MODE>
 void launch_trace_sph(const rspt_scene_s* s, const TraceCall& c, uint32_t* xcur) {
-    const SceneDev& sc = s->dev;
     const TracePre p = trace_pre(c, false);
-    uint32_t* n_overflow = c.cursor + 2;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(p.pgrid), dim3(RSPT_PW_BLOCK), 0, p.stream, sc, s->tex, s->w4, s->big_leaves, s->w4_root, c.queue, c.count_ptr, c.count_imm, c.cursor,
-                           c.ra, c.rb, c.oa, c.ob, c.occ, c.hits, n_overflow, p.ovf, p.spill, (uint32_t)RSPT_W4_SPILL, p.refill, p.leaf, s->w4_top, nullptr, xcur, p.chunk);
-    };
+    auto go = [&](auto kern) { launch_w4(kern, p.pgrid, RSPT_PW_BLOCK, 0, s, c, p, p.leaf, (uint32_t)RSPT_W4_SPILL, nullptr, xcur, p.chunk); };
     if (s->has_quadrics) {   // ABI 27: a disk or a cylinder in the scene: the kernels whose leaf phase reads the slot's kind (trace_w4.h k_trace_w4quad)
         if (OUT_MODE == 1 && getenv("RSPT_VERBOSE"))   // (the trace hook only: a render launches this hundreds of times)
             fprintf(stderr, "rspt: trace instantiation 'k_trace_w4quad<%s, alpha %d>'\n", ANY ? "any" : "closest", !s->has_alpha ? 0 : (s->alpha_simple ? 2 : 1));
@@ -278,41 +281,40 @@ typedef void (*ShadeKernel)(RSPT_SHADE_ARGS);
 // k_shade seconds per step): generic 212 VGPRs 423 / 1685 (0.161 / 0.578 s); diffuse 158 VGPRs = 3 waves as compiled 459 (0.111 s), forced to
 // 4 waves 455; plastic 173 VGPRs as compiled 1749 (0.531 s), 168 + 24 B of spills = 3 waves 1841 (0.470 s), 128 + 152 B = 4 waves 1791.
 struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */
-                      ShadeKernel f_natural, f_w3, f_w4, f_move; /* the fast-math builds of the same four (kernels.h k_shade_fast*, tu_shade_f*.hip); nullptr: the set has none */ };
+                      ShadeKernel f_natural, f_w3, f_w4, f_move; /* the fast-math builds of the same four (kernels.h k_shade_fast*, the SHADE_F* groups of tu_decl.h); nullptr: the set has none */ };
+// A row names its set once.  _W: a set run at 3 waves by default, its MOVE form built so; W4 = the build behind w4 (the Halton sets have none for 4 waves: 3 again).
+// _N: a set run as compiled, its MOVE form too.  Both with their fast-math twins.  _PLAIN: one build, no MOVE form, no fast twins.
+#define RSPT_SV_ROW_W(F, NAME, W4) \
+    {F, NAME, k_shade<F>, k_shade_w<F, 3>, k_shade_w<F, W4>, 3, k_shade_mw<F, 3>, k_shade_fast<F>, k_shade_fast_w<F, 3>, k_shade_fast_w<F, W4>, k_shade_fast_mw<F, 3>}
+#define RSPT_SV_ROW_N(F, NAME) {F, NAME, k_shade<F>, k_shade_w<F, 3>, k_shade_w<F, 4>, 0, k_shade_m<F>, k_shade_fast<F>, k_shade_fast_w<F, 3>, k_shade_fast_w<F, 4>, k_shade_fast_m<F>}
+#define RSPT_SV_ROW_PLAIN(F, NAME) {F, NAME, k_shade<F>, k_shade<F>, k_shade<F>, 0, nullptr}
 const ShadeVariant g_shade_variants[] = {
-    {SV_DIFFUSE, "diffuse", k_shade<SV_DIFFUSE>, k_shade_w<SV_DIFFUSE, 3>, k_shade_w<SV_DIFFUSE, 4>, 3, k_shade_mw<SV_DIFFUSE, 3>,
-     k_shade_fast<SV_DIFFUSE>, k_shade_fast_w<SV_DIFFUSE, 3>, k_shade_fast_w<SV_DIFFUSE, 4>, k_shade_fast_mw<SV_DIFFUSE, 3>},   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
-                                                                                                           //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
-    {SV_PLASTIC, "plastic", k_shade<SV_PLASTIC>, k_shade_w<SV_PLASTIC, 3>, k_shade_w<SV_PLASTIC, 4>, 3, k_shade_mw<SV_PLASTIC, 3>,
-     k_shade_fast<SV_PLASTIC>, k_shade_fast_w<SV_PLASTIC, 3>, k_shade_fast_w<SV_PLASTIC, 4>, k_shade_fast_mw<SV_PLASTIC, 3>},
-    {SV_TEXTURED, "textured", k_shade<SV_TEXTURED>, k_shade_w<SV_TEXTURED, 3>, k_shade_w<SV_TEXTURED, 4>, 0, k_shade_m<SV_TEXTURED>,
-     k_shade_fast<SV_TEXTURED>, k_shade_fast_w<SV_TEXTURED, 3>, k_shade_fast_w<SV_TEXTURED, 4>, k_shade_fast_m<SV_TEXTURED>},
-    {SV_DIFFUSE_H, "diffuse-halton", k_shade<SV_DIFFUSE_H>, k_shade_w<SV_DIFFUSE_H, 3>, k_shade_w<SV_DIFFUSE_H, 3>, 3, k_shade_mw<SV_DIFFUSE_H, 3>,
-     k_shade_fast<SV_DIFFUSE_H>, k_shade_fast_w<SV_DIFFUSE_H, 3>, k_shade_fast_w<SV_DIFFUSE_H, 3>, k_shade_fast_mw<SV_DIFFUSE_H, 3>},   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
-    {SV_PLASTIC_H, "plastic-halton", k_shade<SV_PLASTIC_H>, k_shade_w<SV_PLASTIC_H, 3>, k_shade_w<SV_PLASTIC_H, 3>, 3, k_shade_mw<SV_PLASTIC_H, 3>,
-     k_shade_fast<SV_PLASTIC_H>, k_shade_fast_w<SV_PLASTIC_H, 3>, k_shade_fast_w<SV_PLASTIC_H, 3>, k_shade_fast_mw<SV_PLASTIC_H, 3>},
-    {SV_TEXTURED_H, "textured-halton", k_shade<SV_TEXTURED_H>, k_shade_w<SV_TEXTURED_H, 3>, k_shade_w<SV_TEXTURED_H, 3>, 3, k_shade_mw<SV_TEXTURED_H, 3>,
-     k_shade_fast<SV_TEXTURED_H>, k_shade_fast_w<SV_TEXTURED_H, 3>, k_shade_fast_w<SV_TEXTURED_H, 3>, k_shade_fast_mw<SV_TEXTURED_H, 3>},   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
-    {SV_GENERIC, "generic", k_shade<SV_GENERIC>, k_shade_w<SV_GENERIC, 3>, k_shade_w<SV_GENERIC, 4>, 0, k_shade_m<SV_GENERIC>,
-     k_shade_fast<SV_GENERIC>, k_shade_fast_w<SV_GENERIC, 3>, k_shade_fast_w<SV_GENERIC, 4>, k_shade_fast_m<SV_GENERIC>},
-    {SV_DYNAMIC, "dynamic", k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, k_shade<SV_DYNAMIC>, 0, nullptr},   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
-    {SF_ALL, "moving", k_shade<SF_ALL>, k_shade<SF_ALL>, k_shade<SF_ALL>, 0, nullptr},                     // + moving object instances (dev_scene.h inst_at)
+    RSPT_SV_ROW_W(SV_DIFFUSE, "diffuse", 4),   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
+                                               //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
+    RSPT_SV_ROW_W(SV_PLASTIC, "plastic", 4),
+    RSPT_SV_ROW_N(SV_TEXTURED, "textured"),
+    RSPT_SV_ROW_W(SV_DIFFUSE_H, "diffuse-halton", 3),   // (tu_decl.h: the reference's default sampler gets the narrow builds too)
+    RSPT_SV_ROW_W(SV_PLASTIC_H, "plastic-halton", 3),
+    RSPT_SV_ROW_W(SV_TEXTURED_H, "textured-halton", 3),   // (textured C3 stand-in: 1343 as compiled, 1358 at 3 waves)
+    RSPT_SV_ROW_N(SV_GENERIC, "generic"),
+    RSPT_SV_ROW_PLAIN(SV_DYNAMIC, "dynamic"),   // (its MOVE form needs 256 VGPRs = one wave per SIMD: dynamic materials keep slots for life)   // + lobe lists built per hit (material_assembly.h)
+    RSPT_SV_ROW_PLAIN(SF_ALL, "moving"),        // + moving object instances (dev_scene.h inst_at)
     // scenes with analytic spheres (SF_SPHERE; Sobol' and Halton): the generic / dynamic sets with the sphere arm (dev_bsdf.h shade_sph).  Only
     // sphere scenes take them and sphere scenes take nothing else.  No MOVE form: sphere scenes keep slots for life (the recomputation reads the
     // path's ray by slot).  As compiled: generic-sphere 224 VGPRs, 16 B of scratch, 2 waves / SIMD (generic: 221, 16 B, 2); dynamic-sphere 256 VGPRs
     // + 1 AGPR, 320 B of scratch, ONE wave / SIMD (dynamic: 223, 304 B, 2) — a sphere scene with a dynamic material (a lobe list built per hit: a
     // parameter other than Kd / Ks / roughness varies over the surface) shades at half the occupancy of the triangle set.  Neither rate is measured.
-    {SV_GENERIC_SPH, "generic-sphere", k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, k_shade<SV_GENERIC_SPH>, 0, nullptr},
-    {SV_DYNAMIC_SPH, "dynamic-sphere", k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, k_shade<SV_DYNAMIC_SPH>, 0, nullptr},
+    RSPT_SV_ROW_PLAIN(SV_GENERIC_SPH, "generic-sphere"),
+    RSPT_SV_ROW_PLAIN(SV_DYNAMIC_SPH, "dynamic-sphere"),
     // scenes with a disk or a cylinder (ABI 27, SF_QUADRIC): the two sphere sets with quadric_fill in place of sphere_fill (dev_bsdf.h shade_quad); they serve
     // that scene's spheres and triangles too.  Only such scenes take them and such scenes take nothing else.  Figures: DESIGN section 5.1b.
-    {SV_GENERIC_QUAD, "generic-quadric", k_shade<SV_GENERIC_QUAD>, k_shade<SV_GENERIC_QUAD>, k_shade<SV_GENERIC_QUAD>, 0, nullptr},
-    {SV_DYNAMIC_QUAD, "dynamic-quadric", k_shade<SV_DYNAMIC_QUAD>, k_shade<SV_DYNAMIC_QUAD>, k_shade<SV_DYNAMIC_QUAD>, 0, nullptr},
+    RSPT_SV_ROW_PLAIN(SV_GENERIC_QUAD, "generic-quadric"),
+    RSPT_SV_ROW_PLAIN(SV_DYNAMIC_QUAD, "dynamic-quadric"),
     // scenes with a projection or goniometric light (ABI 24, SF_L_MAP; Sobol' and Halton): the generic and the all-features set with the two arms of
     // light_sample_li / light_is_delta (dev_bsdf.h shade_ml).  Only such scenes take them and such scenes take nothing else.  No MOVE form: the
     // schedule was left off for them (unmeasured there), they keep slots for life.
-    {SV_GENERIC_ML, "generic-maplight", k_shade<SV_GENERIC_ML>, k_shade<SV_GENERIC_ML>, k_shade<SV_GENERIC_ML>, 0, nullptr},
-    {SV_ALL_ML, "all-maplight", k_shade<SV_ALL_ML>, k_shade<SV_ALL_ML>, k_shade<SV_ALL_ML>, 0, nullptr},
+    RSPT_SV_ROW_PLAIN(SV_GENERIC_ML, "generic-maplight"),
+    RSPT_SV_ROW_PLAIN(SV_ALL_ML, "all-maplight"),
 };
 // RSPT_SHADE_VARIANT = name forces an instantiation (it must cover the scene), RSPT_SHADE_WAVES = 0 | 3 | 4 one of its builds (A/B)
 // move_out (may be null): the MOVE form of the chosen set when it has one and the build asked for is its default (RSPT_SHADE_WAVES A/B runs stay on the slot-for-life kernels)

@@ -2,7 +2,7 @@
 // Host code of librspt.hip, included there once inside its anonymous namespace.
 // k_lane_dl<INST, ALPHA, ANIM, WH> by [whitted][0 plain | 1 object instances | 2 moving instances][alpha] (tu_decl.h: the ANIM forms exist with INST only)
 #define RSPT_LANE_ROWS(WH) {{k_lane_dl<false, false, false, WH>, k_lane_dl<false, true, false, WH>}, {k_lane_dl<true, false, false, WH>, k_lane_dl<true, true, false, WH>}, {k_lane_dl<true, false, true, WH>, k_lane_dl<true, true, true, WH>}}
-typedef void (*LaneKernel)(SceneDev, TexTables, LightDistDev, RenderDev, Batch, PathBuf, const uint32_t*, LaneDesc);
+typedef void (*LaneKernel)(RSPT_LANE_ARGS);
 const LaneKernel g_lane_dl[2][3][2] = {RSPT_LANE_ROWS(false), RSPT_LANE_ROWS(true)};
 #undef RSPT_LANE_ROWS
     // the claimed voxels' rows: contributions of every light, the row's distribution, the table entries; returns how many were claimed

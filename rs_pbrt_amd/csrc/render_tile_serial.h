@@ -4,7 +4,7 @@
 // which exist with INST only (tu_decl.h)
 #define RSPT_TS_ROW(M) {{k_tile_serial<false, false, M>, k_tile_serial<false, true, M>}, {k_tile_serial<true, false, M>, k_tile_serial<true, true, M>}}
 #define RSPT_TS_ROW_INST(M) {{nullptr, nullptr}, {k_tile_serial<true, false, M>, k_tile_serial<true, true, M>}}
-typedef void (*TileKernel)(SceneDev, TexTables, LightDistDev, RenderDev, PathBuf, PixDesc, const TileRec*, uint32_t, uint32_t, int32_t, int32_t, float4*, float2*, uint32_t, uint32_t*);
+typedef void (*TileKernel)(RSPT_TS_ARGS);
 const TileKernel g_tile_serial[11][2][2] = {RSPT_TS_ROW(0), RSPT_TS_ROW(1), RSPT_TS_ROW(2), RSPT_TS_ROW(3), RSPT_TS_ROW(4), RSPT_TS_ROW_INST(5), RSPT_TS_ROW_INST(6), RSPT_TS_ROW_INST(7), RSPT_TS_ROW_INST(8), RSPT_TS_ROW(9), RSPT_TS_ROW_INST(10)};
 #undef RSPT_TS_ROW_INST
 #undef RSPT_TS_ROW

@@ -49,10 +49,11 @@ struct PixDesc {              // the sampler's parameters and this render's vect
 #else
 #define RSPT_TS_ATTR
 #endif
+#define RSPT_TS_ARGS                                                                                                                                                   \
+    SceneDev sc, TexTables tt, LightDistDev ld, RenderDev rd, PathBuf pb, PixDesc pd, const TileRec* __restrict__ tiles, uint32_t n_tiles, uint32_t lanes_per_wave,    \
+        int32_t row0, int32_t row1, float4* __restrict__ samp_L, float2* __restrict__ samp_pf, uint32_t max_iters, uint32_t* __restrict__ truncated
 template <bool INST, bool ALPHA, int MODE = 0>
-__global__ __launch_bounds__(64) RSPT_TS_ATTR void k_tile_serial(SceneDev sc, TexTables tt, LightDistDev ld, RenderDev rd, PathBuf pb, PixDesc pd, const TileRec* __restrict__ tiles,
-                                                    uint32_t n_tiles, uint32_t lanes_per_wave, int32_t row0, int32_t row1, float4* __restrict__ samp_L,
-                                                    float2* __restrict__ samp_pf, uint32_t max_iters, uint32_t* __restrict__ truncated) {
+__global__ __launch_bounds__(64) RSPT_TS_ATTR void k_tile_serial(RSPT_TS_ARGS) {
     __shared__ uint32_t stack[RSPT_LDS_STACK * 64];   // 32 levels x the block's 64 columns
     if (threadIdx.x >= lanes_per_wave) return;
     const uint32_t t = blockIdx.x * lanes_per_wave + threadIdx.x;

@@ -78,11 +78,7 @@ RDEV uint32_t pb_next_group(const PbRays<R>& q, uint64_t (&todo)[R], uint64_t (&
 }
 
 template <int OUT_MODE, int R>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pb(SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                              const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                              float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
-                                                              uint32_t chunk, const float4* __restrict__ leaf_boxes) {
+__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pb(RSPT_PK_ARGS) {
     __shared__ uint4 stack_s[RSPT_PK_WAVES * RSPT_W4_MAX_STACK];   // a packet handed to pk_trace_packet: as in k_trace_w4pf; the bundle walk: (ref, L) pairs in the first half of a wave's share
     uint4* const stk = stack_s + (threadIdx.x >> 6) * RSPT_W4_MAX_STACK;
     constexpr uint32_t BUNDLE = 64u * R;

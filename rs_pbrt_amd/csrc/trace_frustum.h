@@ -166,11 +166,7 @@ struct PfFrustum {
 };
 
 template <int OUT_MODE>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pf(SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                              const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                              float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
-                                                              uint32_t chunk, const float4* __restrict__ leaf_boxes) {
+__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pf(RSPT_PK_ARGS) {
     __shared__ uint4 stack_s[RSPT_PK_WAVES * RSPT_W4_MAX_STACK];   // the masked walk: (ref, mask low, mask high, unused); the frustum walk: (ref, L) pairs in the first half of a wave's share
     pk_trace_body<OUT_MODE, PfFrustum>(stack_s + (threadIdx.x >> 6) * RSPT_W4_MAX_STACK, sc, recs, big_leaves, root_ref, queue, count_ptr, count_imm, cursor, rays_a, rays_b, out_a, out_b, out_hits,
                                        chunk, leaf_boxes);

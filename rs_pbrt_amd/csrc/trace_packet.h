@@ -48,7 +48,7 @@ RDEV uint2 pk_load2(const uint2* p) {
 }
 
 #ifdef RSPT_PK_COUNT   // timing-only A/B build (tools/ab_build.sh AB_DEFS=-DRSPT_PK_COUNT): records fetched, leaves tested, packets walked, summed per kernel family
-static __device__ unsigned long long g_pk_count[3];   // one copy per translation unit: read where the kernels are instantiated (tu_w4pk.hip / tu_w4pf.hip)
+static __device__ unsigned long long g_pk_count[3];   // one copy per translation unit: read where the kernels are instantiated (tu.hip, groups W4PK / W4PF / W4PB)
 #define RSPT_PK_COUNT_ADD(i) do { if (__lane_id() == 0) atomicAdd(&g_pk_count[i], 1ull); } while (0)
 #else
 #define RSPT_PK_COUNT_ADD(i) do { } while (0)
@@ -257,12 +257,13 @@ RDEV void pk_trace_body(uint4* stk, const SceneDev& sc, const Wide4Node* __restr
     }
 }
 
+// The parameters of the three packet kernels (k_trace_w4pk here, k_trace_w4pf in trace_frustum.h, k_trace_w4pb in trace_bundle.h), said once
+#define RSPT_PK_ARGS                                                                                                                                            \
+    SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref, const uint32_t* __restrict__ queue,                \
+        const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor, const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,  \
+        float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits, uint32_t chunk, const float4* __restrict__ leaf_boxes
 template <int OUT_MODE>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(SceneDev sc, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                              const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                              const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                              float4* __restrict__ out_a, float4* __restrict__ out_b, rspt_hit* __restrict__ out_hits,
-                                                              uint32_t chunk, const float4* __restrict__ leaf_boxes) {
+__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_PK_ATTR void k_trace_w4pk(RSPT_PK_ARGS) {
     __shared__ uint4 stack_s[RSPT_PK_WAVES * RSPT_W4_MAX_STACK];   // (ref, mask low, mask high, unused)
     pk_trace_body<OUT_MODE, PkMaskedOnly>(stack_s + (threadIdx.x >> 6) * RSPT_W4_MAX_STACK, sc, recs, big_leaves, root_ref, queue, count_ptr, count_imm, cursor, rays_a, rays_b, out_a, out_b, out_hits,
                                           chunk, leaf_boxes);

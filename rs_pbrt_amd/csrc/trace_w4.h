@@ -143,15 +143,16 @@ RDEV bool w4_quadric_leaf(const SphereDev* rec, f3 o, f3 d, float t_max, float* 
     if constexpr (QUAD) return quadric_test(*reinterpret_cast<const QuadricDev*>(rec), o, d, t_max, t_out);
     else return sphere_test(rec->s, o, d, t_max, t_out);
 }
+// The parameters of k_trace_w4 and k_trace_w4quad, said once: the definitions here, the instantiations of tu_decl.h.  chunk: rays a wave claims per global atomic (a multiple of 64)
+#define RSPT_W4_ARGS                                                                                                                                                  \
+    SceneDev sc, TexTables tt, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref, const uint32_t* __restrict__ queue,        \
+        const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor, const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,        \
+        float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ, rspt_hit* __restrict__ out_hits, uint32_t* n_overflow,                 \
+        uint32_t* __restrict__ overflow_list, uint2* __restrict__ spill, uint32_t spill_rows, int refill_thresh, int leaf_thresh, uint32_t n_top,                      \
+        uint32_t* __restrict__ out_inst, uint32_t* xcd_cursors, uint32_t chunk
 template <bool ANY, int OUT_MODE, bool INST, int ALPHA /* 0: no masks, 1: alpha_pass (any texture graph, a call), 2: alpha_simple (in line) */, bool ANIM = false,
           int BLOCK = RSPT_PW_BLOCK, int TOPCAP = RSPT_W4_TOP, bool SPH = false>
-__global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, TexTables tt, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                           const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                           const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                           float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,
-                                                           rspt_hit* __restrict__ out_hits, uint32_t* n_overflow, uint32_t* __restrict__ overflow_list,
-                                                           uint2* __restrict__ spill, uint32_t spill_rows, int refill_thresh, int leaf_thresh, uint32_t n_top,
-                                                           uint32_t* __restrict__ out_inst, uint32_t* xcd_cursors, uint32_t chunk /* rays a wave claims per global atomic (a multiple of 64) */) {
+__global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(RSPT_W4_ARGS) {
     constexpr bool QUAD = false;   // (the quadric arm lives in k_trace_w4quad below: this template's parameters, and so its instantiations' names, stay as they were)
 #include "trace_w4_body.h"
 }
@@ -164,13 +165,7 @@ __global__ __launch_bounds__(BLOCK) RSPT_W4_ATTR void k_trace_w4(SceneDev sc, Te
 #define RSPT_W4_ATTR_QUAD __attribute__((amdgpu_waves_per_eu(1, 8)))
 #endif
 template <bool ANY, int OUT_MODE, int ALPHA>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_W4_ATTR_QUAD void k_trace_w4quad(SceneDev sc, TexTables tt, const Wide4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                           const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                           const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                           float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,
-                                                           rspt_hit* __restrict__ out_hits, uint32_t* n_overflow, uint32_t* __restrict__ overflow_list,
-                                                           uint2* __restrict__ spill, uint32_t spill_rows, int refill_thresh, int leaf_thresh, uint32_t n_top,
-                                                           uint32_t* __restrict__ out_inst, uint32_t* xcd_cursors, uint32_t chunk) {
+__global__ __launch_bounds__(RSPT_PW_BLOCK) RSPT_W4_ATTR_QUAD void k_trace_w4quad(RSPT_W4_ARGS) {
     constexpr bool INST = false, ANIM = false, SPH = true, QUAD = true;
     constexpr int BLOCK = RSPT_PW_BLOCK, TOPCAP = RSPT_W4_TOP;
 #include "trace_w4_body.h"

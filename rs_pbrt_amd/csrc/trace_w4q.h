@@ -42,15 +42,16 @@ static_assert(sizeof(Quad4Node) == 64, "Quad4Node is four 16-byte loads");
 
 #ifdef RSPT_W4Q_COUNT   // timing-only A/B build (tools/ab_build.sh AB_DEFS=-DRSPT_W4Q_COUNT, tools/w4q_lane_count.py): lane occupancy of the two phases, summed over every launch
 // {node steps issued, lanes active in them, leaf phases issued, lanes active in them, rays ended occluded, rays ended unoccluded, node steps of the occluded rays, leaf visits of the occluded rays}
-static __device__ unsigned long long g_w4q_count[8];   // one copy per translation unit: read where the kernels are instantiated (tu_w4q.hip)
+static __device__ unsigned long long g_w4q_count[8];   // one copy per translation unit: read where the kernels are instantiated (tu.hip, group W4Q)
 #endif
 
+#define RSPT_W4Q_ARGS                                                                                                                                          \
+    SceneDev sc, const Quad4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref, const uint32_t* __restrict__ queue,               \
+        const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor, const rspt_ray* __restrict__ rays, uint32_t* __restrict__ out_occ,        \
+        rspt_hit* __restrict__ out_hits, uint32_t* __restrict__ spill, int refill_thresh, int leaf_thresh, uint32_t n_top, uint32_t chunk,                      \
+        const float4* __restrict__ leaf_boxes
 template <int OUT_MODE>
-__global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(SceneDev sc, const Quad4Node* __restrict__ recs, const uint2* __restrict__ big_leaves, uint32_t root_ref,
-                                                             const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint32_t* cursor,
-                                                             const rspt_ray* __restrict__ rays, uint32_t* __restrict__ out_occ, rspt_hit* __restrict__ out_hits,
-                                                             uint32_t* __restrict__ spill, int refill_thresh, int leaf_thresh, uint32_t n_top, uint32_t chunk,
-                                                             const float4* __restrict__ leaf_boxes) {
+__global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_w4q(RSPT_W4Q_ARGS) {
     constexpr int BLOCK = RSPT_PW_BLOCK;
     __shared__ uint32_t stack[RSPT_W4Q_LDS * BLOCK];
     __shared__ float4 top[4 * RSPT_W4Q_TOP];   // top[j * TOP + r] = j-th 16 bytes of record r

@@ -286,11 +286,12 @@ __global__ __launch_bounds__(RSPT_PW_BLOCK) void k_trace_pw(SceneDev sc, const P
 // Second pass for the rays whose stack outgrew the persistent kernel's LDS column (their queue entries
 // were appended to overflow_list): the 64-entry reference-order loop (kernels.h traverse<>).
 // Returns at once when no ray overflowed (the common case).
+#define RSPT_FIXUP_ARGS                                                                                                                                          \
+    SceneDev sc, TexTables tt, const uint32_t* __restrict__ n_overflow, const uint32_t* __restrict__ overflow_list, const rspt_ray* __restrict__ rays_a,          \
+        const rspt_ray* __restrict__ rays_b, float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,                              \
+        rspt_hit* __restrict__ out_hits, uint32_t* __restrict__ out_inst
 template <bool ANY, int OUT_MODE, bool INST, bool ALPHA, bool ANIM = false>
-__global__ __launch_bounds__(RSPT_TRACE_BLOCK) void k_trace_fixup(SceneDev sc, TexTables tt, const uint32_t* __restrict__ n_overflow, const uint32_t* __restrict__ overflow_list,
-                                                                  const rspt_ray* __restrict__ rays_a, const rspt_ray* __restrict__ rays_b,
-                                                                  float4* __restrict__ out_a, float4* __restrict__ out_b, uint32_t* __restrict__ out_occ,
-                                                                  rspt_hit* __restrict__ out_hits, uint32_t* __restrict__ out_inst) {
+__global__ __launch_bounds__(RSPT_TRACE_BLOCK) void k_trace_fixup(RSPT_FIXUP_ARGS) {
     __shared__ uint32_t stack[RSPT_LDS_STACK * RSPT_TRACE_BLOCK];
     const uint32_t n = *n_overflow;
     for (uint32_t i = blockIdx.x * RSPT_TRACE_BLOCK + threadIdx.x; i < n; i += gridDim.x * RSPT_TRACE_BLOCK) {

@@ -21,13 +21,13 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
 
 
 def tree_source_hash():
-    """sha256 (first 16 hex digits) over the kernel / ABI sources under rs_pbrt_amd/csrc + include/rspt.h as they are ON DISK — the recipe
+    """sha256 (first 16 hex digits) over the kernel / ABI sources and the Makefile under rs_pbrt_amd/csrc + include/rspt.h as they are ON DISK — the recipe
     of csrc/Makefile's SRC_HASH, which compiles the same digest into librspt.so.  Equal to source_hash() exactly when the library was
     built from this tree (tests/test_abi.py checks that)."""
     import glob
     import hashlib
     h = hashlib.sha256()
-    names = sorted(os.path.basename(f).encode() for pat in ("*.h", "*.hip", "*.cpp") for f in glob.glob(os.path.join(_HERE, "csrc", pat)))
+    names = sorted(os.path.basename(f).encode() for pat in ("*.h", "*.hip", "*.cpp", "Makefile") for f in glob.glob(os.path.join(_HERE, "csrc", pat)))
     for n in names:
         h.update(n)
         h.update(open(os.path.join(_HERE, "csrc", n.decode()), "rb").read())

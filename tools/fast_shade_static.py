@@ -1,5 +1,5 @@
 """profiles/fast_shade_static.txt from the resource-usage remarks and the gfx950 assembly of the shade units (tools/static_kernel_facts.sh fast): every fast-math
-shade kernel (k_shade_fast*, tu_shade_f*.hip) beside its exact twin.  usage: python tools/fast_shade_static.py WORK_DIR REPO"""
+shade kernel (k_shade_fast*, the SHADE_F* groups of tu.hip) beside its exact twin.  usage: python tools/fast_shade_static.py WORK_DIR REPO"""
 import re
 import subprocess
 import sys

@@ -1,51 +1,39 @@
-"""Compare the compiler's resource figures of every kernel of librspt.so between two source trees, without a GPU: each tree's rs_pbrt_amd/csrc/*.hip
-is compiled for the device only with -Rpass-analysis=kernel-resource-usage (the Makefile's flags), the remarks are read per mangled kernel name, and the two
-sets are compared.  Prints the file kept as profiles/*_kernel_resource_usage.txt: the kernels whose figures changed or that went away, the new kernels,
-and every kernel of both builds.  Exit status 1 if a kernel of the first tree changed or went away.
-usage: python tools/kernel_resource_diff.py PARENT_TREE THIS_TREE [-j N]      (a tree = a checkout's root; `git worktree add` makes the parent's)"""
+"""Compare the compiler's resource figures of every kernel of librspt.so between two source trees, without a GPU: each tree's own rs_pbrt_amd/csrc/Makefile
+writes the -Rpass-analysis=kernel-resource-usage remarks of every unit, compiled for the device only with that unit's flags (`make unit-remarks`), the remarks
+are read per mangled kernel name, and the two sets are compared.  Prints the file kept as profiles/*_kernel_resource_usage.txt: the kernels whose figures
+changed or that went away, the new kernels, and every kernel of both builds.  Exit status 1 if a kernel of the first tree changed or went away.
+Both trees need a Makefile with the unit-remarks target: a tree from before the one-unit-source build (57 tu_*.hip files) cannot be read.
+usage: python tools/kernel_resource_diff.py PARENT_TREE THIS_TREE [-j N]      (a tree = a checkout's root; `git worktree add` makes the parent's)
+The remarks are kept under each tree's build/obj/*.ru and made again only when a source changed."""
 import argparse
-import concurrent.futures
 import glob
 import os
 import re
 import subprocess
 import sys
 
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC",
-         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
 KEYS = (("vgprs", r" VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("sgprs", r"TotalSGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
         ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("waves", r"Occupancy \[waves/SIMD\]: (\d+)"))
 
 
-FAST_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-Xarch_device", "-fapprox-func"]   # csrc/Makefile FAST_FLAGS: the fast-math shade units, tu_shade_f*.hip
-
-
-def remarks(tu):
-    name = os.path.basename(tu)
-    fast = FAST_FLAGS if name.startswith("tu_shade_f") and name not in ("tu_shade_fc.hip", "tu_shade_fmc.hip") else []   # (the generic set keeps exact division)
-    r = subprocess.run([HIPCC] + FLAGS + fast + [os.path.basename(tu)], cwd=os.path.dirname(tu), stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True, errors="replace")
-    if r.returncode != 0:
-        sys.exit("%s failed on %s:\n%s" % (HIPCC, tu, r.stderr[-2000:]))
-    return r.stderr
-
-
 def figures(tree, jobs):
-    tus = sorted(glob.glob(os.path.join(tree, "rs_pbrt_amd", "csrc", "*.hip")))
+    objdir = os.path.join(os.path.abspath(tree), "build", "obj")
+    r = subprocess.run(["make", "-s", "-j%d" % jobs, "-C", os.path.join(tree, "rs_pbrt_amd", "csrc"), "OBJDIR=" + objdir, "unit-remarks"], stderr=subprocess.PIPE, text=True, errors="replace")
+    if r.returncode != 0:
+        sys.exit("make unit-remarks failed in %s:\n%s" % (tree, r.stderr[-2000:]))
     out = {}
-    with concurrent.futures.ThreadPoolExecutor(jobs) as pool:
-        for text in pool.map(remarks, tus):
-            cur = None
-            for line in text.splitlines():
-                m = re.search(r"Function Name: (\S+)", line)
-                if m:
-                    cur = out.setdefault(m.group(1), {})
-                    continue
-                if cur is not None:
-                    for key, pat in KEYS:
-                        m = re.search(pat, line)
-                        if m:
-                            cur[key] = int(m.group(1))
+    for ru in sorted(glob.glob(os.path.join(objdir, "*.ru"))):
+        cur = None
+        for line in open(ru, errors="replace"):
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                cur = out.setdefault(m.group(1), {})
+                continue
+            if cur is not None:
+                for key, pat in KEYS:
+                    m = re.search(pat, line)
+                    if m:
+                        cur[key] = int(m.group(1))
     return out
 
 
