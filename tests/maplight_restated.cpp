@@ -321,6 +321,17 @@ int ml_sample_li(const rspt_scene_desc* sd, uint32_t index, const float p[3], fl
     std::memcpy(out, r, sizeof r);
     return 0;
 }
+// ml_map / ml_sample_li over n directions / reference points (tests/test_reference_light_functions.py runs 2^17 of them): w, p n x 3; out n x 3 / n x 10
+int ml_map_n(const rspt_scene_desc* sd, uint32_t index, const float* w, uint64_t n, float* out) {
+    for (uint64_t i = 0; i < n; i++)
+        if (ml_map(sd, index, w + 3 * i, out + 3 * i) != 0) return -1;
+    return 0;
+}
+int ml_sample_li_n(const rspt_scene_desc* sd, uint32_t index, const float* p, uint64_t n, float* out) {
+    for (uint64_t i = 0; i < n; i++)
+        if (ml_sample_li(sd, index, p + 3 * i, out + 10 * i) != 0) return -1;
+    return 0;
+}
 // The light distribution of (scene, strategy) at p, as rspt_light_distribution reports it: func[n_lights], cdf[n_lights + 1], the grid and p's voxel
 int ml_light_distribution(const rspt_scene_desc* sd, uint32_t strategy, const float p[3], float* func_out, float* cdf_out, int32_t nvox_out[3], int32_t voxel_out[3]) {
     if (!sd || !sd->n_lights) return -1;

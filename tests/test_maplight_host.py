@@ -138,6 +138,11 @@ def test_projection_branches(restated, oracle):
     assert restated.ml_sample_li(C.addressof(sc.desc), 0, p.ctypes.data, out.ctypes.data) == 0
     d2 = float((p.astype(np.float64) ** 2).sum())
     assert np.allclose(out[:3], np.array([2, 3, 4]) * gradient(2, 4)[1, 2] / d2, rtol=1e-5) and out[6] == 1.0
+    # and to the bit: i * projection(-wi) / d^2 in f32, over the very direction sample_li hands to projection (the text's value of each piece: tests/test_reference_light_functions.py)
+    m = ml_map(restated, sc, 0, -out[3:6])
+    d = (lt["p"][:3] - p).astype(F32)
+    d2f = F32(F32(F32(d[0] * d[0]) + F32(d[1] * d[1])) + F32(d[2] * d[2]))
+    assert np.array_equal(out[:3], ((np.array([2, 3, 4], F32) * m).astype(F32) / d2f).astype(F32)) and m.min() > 0
     assert np.allclose(out[3:6], -p / math.sqrt(d2), atol=1e-6) and np.array_equal(out[7:10], lt["p"][:3])
 
 
@@ -184,6 +189,11 @@ def test_restated_power_distribution(restated, oracle):
     f, c, _, _ = restated_distribution(restated, sc, abi.LIGHTS_POWER, (0, 0, 0))
     cos_w = float(sc.lights[2]["p"][17])
     assert np.allclose(f, [4 * math.pi, 2 * math.pi, 2 * math.pi * (1 - cos_w)], rtol=1e-5) and c[0] == 0 and abs(c[-1] - 1) < 1e-6
+    # and to the bit, term by term in f32: ((map * i) * k) * PI [* (1 - cos_total_width)], then RGBSpectrum::y
+    y = lambda r: F32(F32(F32(F32(0.212671) * r) + F32(F32(0.715160) * r)) + F32(F32(0.072169) * r))      # noqa: E731
+    pi = F32(math.pi)
+    want = [y(F32(F32(4) * pi)), y(F32(F32(F32(0.5) * F32(4)) * pi)), y(F32(F32(F32(2) * pi) * F32(F32(1) - sc.lights[2]["p"][17])))]
+    assert np.array_equal(f, np.array(want, F32))
 
 
 # ---- scenes.py's builders against the reference's formulas, evaluated here in f32 ----
