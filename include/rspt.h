@@ -92,10 +92,10 @@ typedef struct {
  * t_shape_hit.v.  Served: rspt_trace / rspt_trace_device, RSPT_LIBM_SPHERE, and rspt_render of spheres as SURFACES (hit, shaded, textured,
  * blocking light) under RSPT_INTEGRATOR_PATH and RSPT_INTEGRATOR_AO with the Sobol' / Halton samplers; rspt_light_distribution serves a
  * sphere scene whose spheres are no lights.  rspt_render answers RSPT_E_UNSUPPORTED ("sphere" and what is missing) for a scene with an
- * emissive sphere (sphere area lights: rspt_light_distribution answers the same), for the directlighting / whitted / volpath integrators
+ * emissive sphere (sphere area lights: rspt_light_distribution answers the same; by default: rspt_set_sphere_lights below serves them), for the directlighting / whitted / volpath integrators
  * and the pixel samplers, and for a sphere scene whose spatial light table is too large to build up front (more bytes than
  * RSPT_LIGHT_TABLE_EAGER_BYTES, 1 GiB by default: many thousand lights; the on-demand voxels find a hit's voxel from triangle barycentrics):
- * the caller keeps its CPU loop.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED, "sphere"): spheres together with object instances.  A DIFFUSE_AREA rspt_light may name a sphere primitive (rendering it is the follow-up). */
+ * the caller keeps its CPU loop.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED, "sphere"): spheres together with object instances.  A DIFFUSE_AREA rspt_light may name a sphere primitive (rendered while the sphere-light gate is on). */
 typedef struct {
     float object_to_world[16];
     float world_to_object[16];
@@ -635,6 +635,24 @@ enum { RSPT_SHADE_MATH_EXACT = 0, RSPT_SHADE_MATH_FAST = 1 };
 int rspt_set_shade_math(uint32_t mode);
 uint32_t rspt_get_shade_math(void);
 
+/* The sphere-light gate (additive to ABI 27; process-wide, host only, needs no rspt_init): 0 = off (the default), 1 = on.
+ *   Off: a scene with an emissive sphere (a DIFFUSE_AREA rspt_light whose prim is a sphere primitive) is answered as before this gate existed, word for word.
+ *   On:  a sphere scene with an emissive sphere (full or clipped, one- or two-sided, either orientation, any transform rspt_scene_create accepts) is served by
+ *        rspt_render / _device / _samples under RSPT_INTEGRATOR_PATH with the Sobol' / Halton samplers and all three light strategies (shade-stage
+ *        instantiations of its own, "generic-spherelight" / "dynamic-spherelight": DiffuseAreaLight over Sphere::sample_with_ref_point / pdf_with_ref_point,
+ *        exact under either shade-math mode), under RSPT_INTEGRATOR_AO (it reads no lights), and by rspt_light_distribution under all three strategies
+ *        (power: Sphere::area in DiffuseAreaLight::power; spatial: 128 points per voxel through sample_li with a bare reference point).
+ *        Still RSPT_E_UNSUPPORTED, the text keeping "sphere area light" and naming what is missing: the directlighting / whitted / volpath integrators, the
+ *        pixel samplers, an emissive sphere next to a disk or a cylinder, a projection / goniometric light next to it, a spatial light table too large to
+ *        build up front (more bytes than RSPT_LIGHT_TABLE_EAGER_BYTES), RSPT_COUNTERS, and a scene with more four-box records than a reference holds.
+ *   Why a gate: what these functions are held to is a hand restatement of src/shapes/sphere.rs:361-504 (tests/spherelight_restated.cpp), not code compiled
+ *        from the reference's text; a light kind that rests on reading is served only to a caller who asked for it.
+ * rspt_set_sphere_lights: a value above 1 is RSPT_E_INVALID (the text names sphere_lights) and leaves the gate as it was.  The environment variable
+ * RSPT_SPHERE_LIGHTS = 0 | 1, when set and non-empty, overrides the call (rspt_get_sphere_lights keeps answering what the call set); any other value makes
+ * a call that meets an emissive sphere answer RSPT_E_INVALID naming RSPT_SPHERE_LIGHTS.  Read by the render entries and rspt_light_distribution at the call. */
+int rspt_set_sphere_lights(uint32_t on);
+int rspt_get_sphere_lights(void);
+
 /* Select the HIP device (ordinal among visible devices) and create streams.
  * Must be called once per process before any other call. */
 int rspt_init(int32_t device);
@@ -789,6 +807,19 @@ int rspt_libm(uint32_t fn, const float* x, const float* y, uint64_t n, float* ou
  * the shading frame n, dpdu, dpdv, dndu, dndv (out[25..39]) after transform_surface_interaction, out[43] = intersect_p's result.  With
  * RSPT_MESH_SPHERE the answer is RSPT_LIBM_SPHERE's.  Any other shape: RSPT_E_INVALID. */
 int rspt_quadric_intersect(uint32_t shape, const float* x, uint64_t n, float* out);
+
+/* Stage-level hook (additive to ABI 27; works with the sphere-light gate off).  Replaces: Sphere::area / sample / sample_with_ref_point /
+ * pdf_with_ref_point (src/shapes/sphere.rs:361-504) and DiffuseAreaLight::sample_li over that shape (src/lights/diffuse.rs:64-84), as the
+ * sphere-light shade sets and light-table kernels call them (rs_pbrt_amd/csrc/dev_sphere_light.h).  64 floats per element in and out.
+ *   x[0..41]  the 42 words of one rspt_sphere;  x[42] a flags word (its BITS: non-zero = the light is two-sided);
+ *   x[43..45] the reference point's p, x[46..48] its p_error, x[49..51] its n (a bare point: p_error = n = 0);  x[52..53] u;  x[54..56] a query direction wi.
+ *   out[0]      Sphere::area
+ *   out[1..10]  Sphere::sample(u): p[3], p_error[3], n[3], pdf
+ *   out[11..20] Sphere::sample_with_ref_point(ref, u): p[3], p_error[3], n[3], pdf
+ *   out[21..27] DiffuseAreaLight::sample_li(ref, u) of L = 1: radiance[3], wi[3] (0 when the sample is black before wi is formed), pdf
+ *   out[28]     Sphere::pdf_with_ref_point(ref, wi)
+ * Unused words are 0 on output and ignored on input. */
+int rspt_sphere_light(const float* x, uint64_t n, float* out);
 
 /* Benchmark hook: same as rspt_trace on rays already resident in device memory,
  * repeated `repeat` times; returns average kernel milliseconds per launch. */

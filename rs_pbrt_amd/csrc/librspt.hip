@@ -280,7 +280,7 @@ struct rspt_scene_s {
     const char* maplight_kinds = "";   // "projection", "goniometric" or "projection and goniometric": which of the two the scene holds, for the refusals
     bool has_maplights = false;       // ABI 24: a projection or goniometric light (dev_scene.h light_sample_li's two arms); rspt_render serves them under path (Sobol', Halton) and ao
     bool has_spheres = false;         // ABI 23: analytic spheres behind the triangle records (dev_sphere.h); rspt_render serves them under path / ao (Sobol', Halton)
-    bool has_sphere_light = false;    // an emissive sphere: refused by rspt_render and the light-distribution hook (sphere area lights are not on the device)
+    bool has_sphere_light = false;    // an emissive sphere: refused by rspt_render and the light-distribution hook unless the sphere-light gate is on (rspt_set_sphere_lights)
     // ABI 27: a disk or a cylinder (dev_quadric.h).  Such a scene also sets has_spheres — its records sit in the sphere slots and it takes every path a sphere scene
     // takes — and has_quadrics picks the instantiations that read a slot's kind.  quadric_kinds / quadric_light_kinds: "disk", "cylinder" or "disk and cylinder", for the refusals
     bool has_quadrics = false, has_disks = false, has_cylinders = false;
@@ -508,7 +508,19 @@ int round_up_pow2_32(int32_t v) {  // pbrt.rs:188-198
     return v + 1;
 }
 
+// ---- the sphere-light gate (include/rspt.h rspt_set_sphere_lights): host-only, process-wide, off by default ----
+std::atomic<uint32_t> g_sphere_lights{0u};
+// the gate a call runs under: RSPT_SPHERE_LIGHTS = 0 | 1 when set and non-empty, else what rspt_set_sphere_lights left; -1: the variable holds something else
+int sphere_lights_mode() {
+    const char* e = getenv("RSPT_SPHERE_LIGHTS");
+    if (!e || !*e) return (int)g_sphere_lights.load();
+    if (!strcmp(e, "0")) return 0;
+    if (!strcmp(e, "1")) return 1;
+    return -1;
+}
+
 // Light distribution for (scene, strategy): create_light_sample_distribution (lightdistrib.rs:393-418)
+// (a scene with an emissive sphere reaches this only while the sphere-light gate is on: its tables come from the kernels that carry the sphere arm)
 int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const LightDist** lazy_out = nullptr) {
     const uint32_t nl = s->dev.n_lights;
     *out = LightDistDev{};
@@ -541,6 +553,7 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             if (lazy) n_rows = std::max<uint64_t>(1, std::min<uint64_t>(n_vox, env_size("RSPT_LIGHT_TABLE_POOL_BYTES", (size_t)16 << 30) / row_bytes));
             // (the on-demand kernels carry no projection / goniometric arm: such a scene takes the table built up front or nothing)
             if (lazy && s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)", s->maplight_kinds);
+            if (lazy && s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES): the on-demand kernels carry no sphere area light");
             if (n_rows > 0x7fffffffull || n_vox > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "spatial light distribution: %llu voxels", (unsigned long long)n_vox);
         }
         int rc;
@@ -555,10 +568,10 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             HIP_TRY(hipMemcpyAsync(d.lazy, &lz, sizeof lz, hipMemcpyHostToDevice, g.stream));
         } else if (eff == RSPT_LIGHTS_SPATIAL) {
             uint64_t total = n_vox * nl;
-            hipLaunchKernelGGL(s->has_maplights ? k_ld_contrib_ml : k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
+            hipLaunchKernelGGL(s->has_sphere_light ? k_ld_contrib_sl : s->has_maplights ? k_ld_contrib_ml : k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
             hipLaunchKernelGGL(k_ld_build, dim3((uint32_t)((n_vox + 255) / 256)), dim3(256), 0, g.stream, (uint32_t)n_vox, nl, 0, d.func, d.cdf, d.func_int);
         } else {
-            hipLaunchKernelGGL(s->has_maplights ? k_ld_fixed_ml : k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
+            hipLaunchKernelGGL(s->has_sphere_light ? k_ld_fixed_sl : s->has_maplights ? k_ld_fixed_ml : k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
             hipLaunchKernelGGL(k_ld_build, dim3(1), dim3(64), 0, g.stream, 1u, nl, 1, d.func, d.cdf, d.func_int);
         }
         HIP_TRY(hipGetLastError());
@@ -756,6 +769,13 @@ int rspt_set_shade_math(uint32_t mode) {
     return RSPT_OK;
 }
 uint32_t rspt_get_shade_math(void) { return g_shade_math.load(); }
+// the sphere-light gate: host-only state, no device needed (sphere_lights_mode above; rspt_light_distribution reads it at the call)
+int rspt_set_sphere_lights(uint32_t on) {
+    if (on > 1u) return fail(RSPT_E_INVALID, "sphere_lights = %u: 0 (off, the default) or 1 (on)", on);
+    g_sphere_lights.store(on);
+    return RSPT_OK;
+}
+int rspt_get_sphere_lights(void) { return (int)g_sphere_lights.load(); }
 // Replaces: BVHAccel::new (bvh.rs:96-392), on the device; see bvh_device.h
 int64_t rspt_bvh_build_gpu(const float* P, uint64_t n_vertices, const uint32_t* tri_idx, uint64_t n_tris, uint32_t max_prims_in_node,
                            rspt_bvh_node* nodes_out, uint64_t nodes_cap, uint32_t* ordered_out) {
@@ -1294,8 +1314,56 @@ __global__ void k_leaf_quadric(uint32_t kind, uint32_t n_words, const float* __r
     float t = 0.0f;
     r[43] = quadric_test(qd, o, d, q[6], &t) ? 1.0f : 0.0f;
 }
+// rspt_sphere_light: one rspt_sphere (42 words), a flags word (non-zero: two-sided), the reference point's p, p_error, n, u[2] and a query direction wi ->
+// Sphere::area / sample / sample_with_ref_point / pdf_with_ref_point and DiffuseAreaLight::sample_li of L = 1 (dev_sphere_light.h); 64 floats in and out
+__global__ void k_sphere_light(const float* __restrict__ x, uint64_t n, float* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rspt_sphere sp;
+    uint32_t* sw = reinterpret_cast<uint32_t*>(&sp);
+    for (int k = 0; k < 42; k++) sw[k] = __float_as_uint(x[64 * i + k]);
+    const float* q = x + 64 * i + 42;
+    rspt_light lt{};
+    lt.kind = RSPT_LIGHT_DIFFUSE_AREA;
+    lt.L[0] = lt.L[1] = lt.L[2] = 1.0f;
+    lt.two_sided = __float_as_uint(q[0]) != 0u;
+    const SlRef ref{f3{q[1], q[2], q[3]}, f3{q[4], q[5], q[6]}, f3{q[7], q[8], q[9]}};
+    const f2 u{q[10], q[11]};
+    const f3 wq{q[12], q[13], q[14]};
+    float* r = out + 64 * i;
+    for (int k = 0; k < 64; k++) r[k] = 0.0f;
+    r[0] = sphere_area(sp);
+    float pdf = 0.0f;
+    LightSample a = sphere_sample(sp, u, &pdf);
+    r[1] = a.p.x; r[2] = a.p.y; r[3] = a.p.z; r[4] = a.p_err.x; r[5] = a.p_err.y; r[6] = a.p_err.z; r[7] = a.n.x; r[8] = a.n.y; r[9] = a.n.z; r[10] = pdf;
+    pdf = 0.0f;
+    a = sphere_sample_ref(sp, ref, u, &pdf);
+    r[11] = a.p.x; r[12] = a.p.y; r[13] = a.p.z; r[14] = a.p_err.x; r[15] = a.p_err.y; r[16] = a.p_err.z; r[17] = a.n.x; r[18] = a.n.y; r[19] = a.n.z; r[20] = pdf;
+    pdf = 0.0f;
+    f3 wi{0.0f, 0.0f, 0.0f};
+    const rgb li = sphere_light_sample_li(sp, lt, ref, u, &wi, &pdf, &a);
+    r[21] = li.r; r[22] = li.g; r[23] = li.b; r[24] = wi.x; r[25] = wi.y; r[26] = wi.z; r[27] = pdf;
+    r[28] = sphere_pdf_ref(sp, ref, wq);
+}
 }  // namespace
 extern "C" {
+int rspt_sphere_light(const float* x, uint64_t n, float* out) {
+    if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
+    if (n == 0) return RSPT_OK;
+    if (!x || !out || n > (1ull << 25)) return fail(RSPT_E_INVALID, "null argument or more than 2^25 elements");
+    HIP_TRY(hipSetDevice(g.device));
+    float *xd = nullptr, *od = nullptr;
+    struct Guard { float **a, **b; ~Guard() { for (float** p : {a, b}) if (*p) (void)hipFree(*p); } } guard{&xd, &od};
+    int rc;
+    if ((rc = dev_alloc(&xd, n * 64)) || (rc = dev_alloc(&od, n * 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(xd, x, n * 64 * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    hipLaunchKernelGGL(k_sphere_light, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, xd, n, od);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, od, n * 64 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RSPT_OK;
+}
+
 int rspt_quadric_intersect(uint32_t shape, const float* x, uint64_t n, float* out) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (shape != RSPT_MESH_SPHERE && shape != RSPT_MESH_DISK && shape != RSPT_MESH_CYLINDER) return fail(RSPT_E_INVALID, "bad shape %#x (RSPT_MESH_SPHERE, RSPT_MESH_DISK, RSPT_MESH_CYLINDER)", shape);
@@ -1342,7 +1410,13 @@ int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3],
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
     // (a scene whose spheres are no lights needs no sphere code here: the spatial voxels take the world bound from the BVH root, which holds the spheres)
     if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: the light distributions are not built for %s yet", s->quadric_light_kinds, s->quadric_light_what);
-    if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
+    if (s->has_sphere_light) {   // served while the sphere-light gate is on (rspt_set_sphere_lights), for a sphere scene the _sl kernels cover; off: today's answer
+        const int sl = sphere_lights_mode();
+        if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
+        if (!sl) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
+        if (s->has_quadrics) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: the sphere area light kernels read sphere records only", s->quadric_kinds);
+        if (s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s light: the sphere area light kernels carry no map light", s->maplight_kinds);
+    }
     // (a scene with projection / goniometric lights: get_light_dist launches the kernels that carry their arms, and refuses the on-demand table)
     const uint32_t nl = s->dev.n_lights;
     if (nl == 0) return fail(RSPT_E_INVALID, "the scene has no lights");

@@ -29,6 +29,7 @@ struct RenderRun {
     uint32_t ns = 1, ao_n = 1, dl_levels = 0, dl_H = 1, dl_R = 1, move_first = 1;
     bool counters = false, ao = false, dl_lane = false, dl_one_round = false, move = false;
     const char* shade_name = "generic"; ShadeKernel shade_k = nullptr, shade_move_k = nullptr;
+    bool sphere_lights = false;   // validate(): the scene holds an emissive sphere and the sphere-light gate is on (rspt_set_sphere_lights): the sphere-light shade sets serve it
     int shade_math = RSPT_SHADE_MATH_EXACT; bool shade_fast = false; char shade_name_fast[48];   // validate(): the mode; size_batches(): whether fast builds serve this render (then shade_name = "<set>-fast")
     // prepare(): the per-lane directlighting forms' arrays, iteration counts, launch geometry, events (kev: per-launch durations, each pair recorded on the
     // stream its kernel runs on — closest-hit, shadow-ray, shade [+ texture])
@@ -114,7 +115,12 @@ int RenderRun::validate() {
         const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
         const char* q = s->quadric_kinds;
         if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: %s are not served on the device yet (%s)", s->quadric_light_kinds, s->quadric_light_what, iname);
-        if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are not served on the device yet (%s)", q, iname);
+        if (s->has_sphere_light) {
+            const int sl = sphere_lights_mode();   // the gate (rspt_set_sphere_lights): off, today's answer; on, still refused: the sphere-light kernels read sphere records only
+            if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
+            if (!sl) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are not served on the device yet (%s)", q, iname);
+            return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are served in scenes without a disk or a cylinder only (%s)", q, iname);
+        }
         if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
             return fail(RSPT_E_UNSUPPORTED, "scene with a %s under the %s integrator: these shapes are served by path and ao only", q, iname);
         if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
@@ -128,7 +134,23 @@ int RenderRun::validate() {
     if (s->has_spheres) {
         static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
         const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
-        if (s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: sphere area lights are not served on the device yet (%s)", iname);
+        if (s->has_sphere_light) {
+            // The gate (rspt_set_sphere_lights).  Off: today's answer.  On: served by path under Sobol' / Halton (the sphere-light shade sets, launch_trace.h) and by ao,
+            // which reads no lights; everything else is refused by name, so the caller keeps its CPU loop.
+            const int sl = sphere_lights_mode();
+            if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
+            if (!sl) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: sphere area lights are not served on the device yet (%s)", iname);
+            if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+                return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere under the %s integrator: sphere area lights are served by path (and ao, which reads no lights) only", iname);
+            if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+                return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere under the %s sampler: sphere area lights are served with the sobol and halton samplers only",
+                            d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                            d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+            if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "scene with a sphere area light and more four-box records than a reference holds");
+            if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with a sphere area light: the sphere traversal keeps no node counters");
+            if (s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light next to a sphere area light: that pair has no shade instantiation", s->maplight_kinds);
+            sphere_lights = true;
+        }
         if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
             return fail(RSPT_E_UNSUPPORTED, "scene with spheres under the %s integrator: spheres are served by path and ao only", iname);
         if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
@@ -434,10 +456,11 @@ int RenderRun::size_batches() {
     // the fast-math builds (rspt_set_shade_math): the path integrator's wavefront form under Sobol' / Halton only, and only the sets that have them; every other render
     // of a fast-mode process runs the exact kernels under the plain name
     const bool want_fast = shade_math == RSPT_SHADE_MATH_FAST && d->integrator == RSPT_INTEGRATOR_PATH && !pixel_sampler;
-    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k, want_fast, &shade_fast);
+    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k, want_fast && !sphere_lights, &shade_fast, sphere_lights);
     if (shade_k && shade_fast) { snprintf(shade_name_fast, sizeof shade_name_fast, "%s-fast", shade_name); shade_name = shade_name_fast; }
     if (!shade_k) return fail(RSPT_E_UNSUPPORTED, s->has_maplights ? "RSPT_SHADE_VARIANT names no instantiation with the projection / goniometric arms (generic-maplight, all-maplight)"
                                                                   : s->has_quadrics ? "RSPT_SHADE_VARIANT names no instantiation with the disk / cylinder arm (generic-quadric, dynamic-quadric)"
+                                                                  : sphere_lights ? "RSPT_SHADE_VARIANT names no instantiation with the sphere area light arms (generic-spherelight, dynamic-spherelight)"
                                                                   : "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");
     move = !volpath && !direct && !ao && !pixel_sampler && !s->has_animated && shade_move_k != nullptr && env_size("RSPT_MOVE", 1) != 0;
     // the first iteration that runs the MOVE kernel.  Iteration 0 reads a dense pixel-major queue whatever the schedule and its stores are dense too (every slot is

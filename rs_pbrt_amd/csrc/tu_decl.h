@@ -135,7 +135,7 @@ RSPT_TU_LANE_WH(true, false, true) RSPT_TU_LANE_WH(true, true, true)
 #endif
 // ---- the shade groups.  The lists that the exact builds (X empty) share with their fast-math twins (X = _fast: kernels.h k_shade_fast*; rspt_set_shade_math,
 // DESIGN section 5.3a).  A fast group is compiled with RSPT_FAST_MATH defined and, but for the generic set's two, without correctly rounded f32 division /
-// square root (csrc/Makefile FAST_GROUPS).  The dynamic, moving, sphere, quadric and map-light sets have no fast build.
+// square root (csrc/Makefile FAST_GROUPS).  The dynamic, moving, sphere, sphere-light, quadric and map-light sets have no fast build.
 #define RSPT_TU_LIST_A(X) \
     RSPT_TU_SHADE(X, SV_DIFFUSE) RSPT_TU_SHADE_W(X, SV_DIFFUSE, 3) RSPT_TU_SHADE_W(X, SV_DIFFUSE, 4) RSPT_TU_SHADE(X, SV_PLASTIC) RSPT_TU_SHADE_W(X, SV_PLASTIC, 3) RSPT_TU_SHADE_W(X, SV_PLASTIC, 4)
 #define RSPT_TU_LIST_B(X) RSPT_TU_SHADE(X, SV_TEXTURED) RSPT_TU_SHADE_W(X, SV_TEXTURED, 3) RSPT_TU_SHADE_W(X, SV_TEXTURED, 4)
@@ -196,6 +196,15 @@ RSPT_TU_LIST_MH(_fast)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_S)
 RSPT_TU_SHADE(, SV_GENERIC_SPH) RSPT_TU_SHADE(, SV_DYNAMIC_SPH)   /* scenes with spheres; no MOVE form: they keep slots for life */
+#endif
+// scenes with spheres that hold a sphere area light, served while the sphere-light gate is on (rspt_set_sphere_lights): the two sphere sets with the
+// sphere-light arms of shade_path (kernels.h k_shade_sl); every kernel above keeps its name and its code
+#define RSPT_TU_SHADE_SL(F) RSPT_TU_X template __global__ void k_shade_sl<F>(RSPT_SHADE_ARGS);
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_SL)
+RSPT_TU_SHADE_SL(SV_GENERIC_SPH)   /* no MOVE form, no fast-math form */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_SLD)
+RSPT_TU_SHADE_SL(SV_DYNAMIC_SPH)
 #endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_Q)
 RSPT_TU_SHADE(, SV_GENERIC_QUAD)   /* scenes with a disk or a cylinder; no MOVE form, as for spheres */

@@ -17,7 +17,8 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
            "rspt_dev_upload", "rspt_dev_download", "rspt_last_error", "rspt_last_counters", "rspt_bvh_build", "rspt_bvh_last_error",
            "rspt_bvh_build_gpu", "rspt_bvh_build_bounds", "rspt_comm_unique_id", "rspt_comm_init", "rspt_comm_destroy", "rspt_light_distribution", "rspt_libm",
            "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library", "rspt_realistic_camera_setup",
-           "rspt_camera_rays", "rspt_quadric_intersect", "rspt_set_shade_math", "rspt_get_shade_math")
+           "rspt_camera_rays", "rspt_quadric_intersect", "rspt_set_shade_math", "rspt_get_shade_math",
+           "rspt_set_sphere_lights", "rspt_get_sphere_lights", "rspt_sphere_light")
 
 
 def tree_source_hash():
@@ -93,6 +94,9 @@ def lib():
         L.rspt_comm_init.argtypes = [i32, i32, vp]
         L.rspt_set_shade_math.argtypes = [u32]
         L.rspt_get_shade_math.restype = u32
+        L.rspt_set_sphere_lights.argtypes = [u32]
+        L.rspt_get_sphere_lights.restype = C.c_int
+        L.rspt_sphere_light.argtypes = [vp, u64, vp]
         _LIB = L
     return _LIB
 
@@ -116,6 +120,37 @@ def set_shade_math(mode):
 def get_shade_math():
     """"exact" or "fast": what set_shade_math last set (the environment's RSPT_SHADE_MATH, which overrides it per render, is not reflected)"""
     return {v: k for k, v in SHADE_MATH.items()}[int(lib().rspt_get_shade_math())]
+
+
+def set_sphere_lights(on):
+    """rspt_set_sphere_lights: True serves scenes with an emissive sphere where include/rspt.h says so (off by default: such a scene is refused).  Process-wide,
+    host only; an integer is passed through as it is, so that a value above 1 meets the library's own refusal."""
+    _check(lib().rspt_set_sphere_lights(int(on)))
+
+
+def get_sphere_lights():
+    """what set_sphere_lights last set (the environment's RSPT_SPHERE_LIGHTS, which overrides it per call, is not reflected)"""
+    return bool(lib().rspt_get_sphere_lights())
+
+
+def sphere_light(spheres, two_sided, ref_p, ref_p_error, ref_n, u, wi):
+    """rspt_sphere_light: records of SPHERE_DT, per element a two-sided flag, the reference point (p, p_error, n), u (n, 2) and a query direction ->
+    (n, 64) f32: [0] area, [1:11] Sphere::sample's p, p_error, n, pdf, [11:21] sample_with_ref_point's, [21:28] DiffuseAreaLight::sample_li's radiance of
+    L = 1, wi, pdf, [28] pdf_with_ref_point(ref, wi).  Compare results as uint32 words: a NaN is a legitimate answer."""
+    x = sphere_light_pack(spheres, two_sided, ref_p, ref_p_error, ref_n, u, wi)
+    out = np.empty_like(x)
+    _check(lib().rspt_sphere_light(x.ctypes.data, len(x), out.ctypes.data))
+    return out
+
+
+def sphere_light_pack(spheres, two_sided, ref_p, ref_p_error, ref_n, u, wi):
+    """the (n, 64) f32 input elements of rspt_sphere_light (include/rspt.h gives the layout); host only"""
+    n = len(spheres)
+    x = np.zeros((n, 64), np.float32)
+    x[:, :42] = np.ascontiguousarray(spheres).view(np.float32).reshape(n, 42)
+    x[:, 42:43].view(np.uint32)[:, 0] = np.asarray(two_sided, bool).astype(np.uint32)
+    x[:, 43:46], x[:, 46:49], x[:, 49:52], x[:, 52:54], x[:, 54:57] = ref_p, ref_p_error, ref_n, u, wi
+    return x
 
 
 def camera_decompose(rd):

@@ -719,7 +719,8 @@ class SceneBuilder:
         """Shape "sphere" (api.rs make_shapes, shapes/sphere.rs:59-84) under the CTM object_to_world (a Transform; its m_inv is world_to_object):
         Sphere::new's clamps, acos and radians in f32 with the host libm.  zmin / zmax default to -radius / radius.  emit = rgb L makes it a
         DiffuseAreaLight (one per sphere).  The library traces spheres (rspt_trace) and renders them as surfaces under the path and ao
-        integrators with the Sobol' / Halton samplers; rspt_render refuses emissive spheres, the other integrators and the pixel samplers."""
+        integrators with the Sobol' / Halton samplers; rspt_render refuses emissive spheres (unless the sphere-light gate is on: lib.set_sphere_lights), the other
+        integrators and the pixel samplers."""
         assert self.cur_object < 0, "spheres inside ObjectBegin / ObjectEnd are not modelled (spheres next to object instances are refused)"
         if material is None:
             material = abi.NO_MATERIAL

@@ -109,6 +109,9 @@ extern "C" {
     pub fn rspt_abi_version() -> c_int;
     pub fn rspt_set_shade_math(mode: u32) -> c_int;                                // process-wide, host only; the environment's RSPT_SHADE_MATH=exact|fast overrides it
     pub fn rspt_get_shade_math() -> u32;
+    pub fn rspt_set_sphere_lights(on: u32) -> c_int;                               // the sphere-light gate (additive to ABI 27): process-wide, host only, off by default; RSPT_SPHERE_LIGHTS=0|1 overrides it
+    pub fn rspt_get_sphere_lights() -> c_int;
+    pub fn rspt_sphere_light(x: *const f32, n: u64, out: *mut f32) -> c_int;       // stage hook: Sphere::area / sample / sample_with_ref_point / pdf_with_ref_point, 64 floats per element
     pub fn rspt_init(device: i32) -> c_int;
     pub fn rspt_shutdown();
     pub fn rspt_scene_create(desc: *const RsptSceneDesc, out: *mut *mut RsptSceneOpaque) -> c_int;
