@@ -116,7 +116,8 @@ typedef struct {
  * emissive one ("disk area light" / "cylinder area light"; rspt_light_distribution answers the same), the directlighting / whitted / volpath
  * integrators, the pixel samplers, a projection or goniometric light beside them, the on-demand light table, more four-box records than a
  * reference holds, and RSPT_COUNTERS.  Refused at rspt_scene_create (RSPT_E_UNSUPPORTED): disks or cylinders together with object
- * instances.  A DIFFUSE_AREA rspt_light may name such a primitive (Disk::sample / Cylinder::sample are the follow-up). */
+ * instances.  A DIFFUSE_AREA rspt_light may name such a primitive (rendered while the quadric-light gate is on: rspt_set_quadric_lights below;
+ * the refusal of an emissive one above is the answer by default). */
 typedef struct {
     float object_to_world[16];
     float world_to_object[16];
@@ -653,6 +654,31 @@ uint32_t rspt_get_shade_math(void);
 int rspt_set_sphere_lights(uint32_t on);
 int rspt_get_sphere_lights(void);
 
+/* The quadric-light gate (additive to ABI 27; process-wide, host only, needs no rspt_init): 0 = off (the default), 1 = on.
+ *   Off: a scene with an emissive disk or cylinder (a DIFFUSE_AREA rspt_light whose prim is a disk or cylinder primitive) is answered as before this gate existed,
+ *        word for word, and so is an emissive sphere next to a disk or a cylinder.
+ *   On:  in a scene with a disk or a cylinder, a shape's area light is served while that shape's gate is on: an emissive disk or cylinder needs this gate, an
+ *        emissive sphere there needs this gate AND the sphere-light gate (this gate alone: RSPT_E_UNSUPPORTED naming "sphere area light" and
+ *        rspt_set_sphere_lights; the sphere-light gate alone: refused as before).  A sphere scene without a disk or a cylinder is untouched by this gate.
+ *        Served: rspt_render / _device / _samples under RSPT_INTEGRATOR_PATH with the Sobol' / Halton samplers and all three light strategies, beside triangle,
+ *        point, spot, distant and infinite lights (shade-stage instantiations of its own, "generic-quadriclight" / "dynamic-quadriclight", exact under either
+ *        shade-math mode), under RSPT_INTEGRATOR_AO (it reads no lights), and by rspt_light_distribution under all three strategies.
+ *        The lights are the reference's as written (src/shapes/disk.rs:207-280, src/shapes/cylinder.rs:331-415, src/lights/diffuse.rs:64-103), not repaired:
+ *        Disk::area = phi_max / 2 * (radius^2 - inner_radius^2) and Cylinder::area = (z_max - z_min) * radius * phi_max are OBJECT-space figures (the
+ *        transform's scale never enters the pdf or the power); Disk::sample draws from the FULL disk of `radius`, ignoring inner_radius and phi_max, so points
+ *        of the cut-away part of an annulus or a partial disk are returned, with pdf 1 / area() of the true area, and carry emission; pdf_with_ref_point runs
+ *        the shape's own intersect, which does honour the clipping, so a BSDF-sampled direction toward a cut-away point has light pdf 0.
+ *        Still RSPT_E_UNSUPPORTED, the text keeping "disk area light" and/or "cylinder area light" and naming what is missing: the directlighting / whitted /
+ *        volpath integrators, the pixel samplers, a projection / goniometric light next to it, a spatial light table too large to build up front (more bytes
+ *        than RSPT_LIGHT_TABLE_EAGER_BYTES), RSPT_COUNTERS, and a scene with more four-box records than a reference holds.
+ *   Why a gate: what these functions are held to is a hand restatement of the reference's text (tests/quadriclight_restated.cpp,
+ *        tests/quadriclight_render_restated.cpp), not code compiled from it; a light kind that rests on reading is served only to a caller who asked for it.
+ * rspt_set_quadric_lights: a value above 1 is RSPT_E_INVALID (the text names quadric_lights) and leaves the gate as it was.  The environment variable
+ * RSPT_QUADRIC_LIGHTS = 0 | 1, when set and non-empty, overrides the call (rspt_get_quadric_lights keeps answering what the call set); any other value makes
+ * a call that consults the gate answer RSPT_E_INVALID naming RSPT_QUADRIC_LIGHTS.  Read by the render entries and rspt_light_distribution at the call. */
+int rspt_set_quadric_lights(uint32_t on);
+int rspt_get_quadric_lights(void);
+
 /* Select the HIP device (ordinal among visible devices) and create streams.
  * Must be called once per process before any other call. */
 int rspt_init(int32_t device);
@@ -820,6 +846,22 @@ int rspt_quadric_intersect(uint32_t shape, const float* x, uint64_t n, float* ou
  *   out[28]     Sphere::pdf_with_ref_point(ref, wi)
  * Unused words are 0 on output and ignored on input. */
 int rspt_sphere_light(const float* x, uint64_t n, float* out);
+
+/* Stage-level hook (additive to ABI 27; works with the quadric-light gate off).  Replaces: Disk::area / sample / sample_with_ref_point / pdf_with_ref_point
+ * (src/shapes/disk.rs:207-280), the same four of Cylinder (src/shapes/cylinder.rs:331-415) and DiffuseAreaLight::sample_li / power over that shape
+ * (src/lights/diffuse.rs:64-93), as the quadric-light shade sets and light-table kernels call them (rs_pbrt_amd/csrc/dev_quadric_light.h).  64 floats per
+ * element in and out.
+ *   x[0..39]  the 40 words of one rspt_disk or rspt_cylinder;  x[40] its kind (its BITS: RSPT_MESH_DISK or RSPT_MESH_CYLINDER; anything else: all 64 output
+ *             words are 0);  x[42] a flags word (its BITS: non-zero = the light is two-sided);
+ *   x[43..45] the reference point's p, x[46..48] its p_error, x[49..51] its n (a bare point: p_error = n = 0);  x[52..53] u;  x[54..56] a query direction wi.
+ *   out[0]      area
+ *   out[1..10]  sample(u): p[3], p_error[3], n[3], pdf
+ *   out[11..20] sample_with_ref_point(ref, u): p[3], p_error[3], n[3], pdf
+ *   out[21..27] DiffuseAreaLight::sample_li(ref, u) of L = 1: radiance[3], wi[3] (0 when the sample is black before wi is formed), pdf
+ *   out[28]     pdf_with_ref_point(ref, wi)
+ *   out[29..31] DiffuseAreaLight::power of L = 1
+ * Unused words are 0 on output and ignored on input. */
+int rspt_quadric_light(const float* x, uint64_t n, float* out);
 
 /* Benchmark hook: same as rspt_trace on rays already resident in device memory,
  * repeated `repeat` times; returns average kernel milliseconds per launch. */

@@ -13,6 +13,7 @@
 #include "dev_texture.h"
 #include "dev_quadric.h"
 #include "dev_sphere_light.h"
+#include "dev_quadric_light.h"
 #include "dev_lens.h"
 #include "pixel_sampler.h"
 
@@ -681,13 +682,34 @@ RDEV rgb light_power_sl(const SceneDev& sc, const rspt_light& lt) {
     }
     return light_power<F>(sc, lt);
 }
+// ---- disk and cylinder area lights (rspt_set_quadric_lights; dev_quadric_light.h): compiled only where QL is set, so every other kernel keeps its code ----
+// The same dispatch for a scene with a disk or a cylinder: the slot behind a record that carries MF_SPHERE is a QuadricDev whose kind picks the disk's, the
+// cylinder's or (an emissive sphere in such a scene) the sphere's light functions.
+template <uint32_t F = 0xffffffffu>
+RDEV rgb light_sample_li_ql(const SceneDev& sc, const rspt_light& lt, const SlRef& ref, f2 u, f3* wi, float* pdf, LightSample* ls) {
+    if (lt.kind == RSPT_LIGHT_DIFFUSE_AREA) {
+        const TriRec t = load_tri(sc, lt.prim);
+        if (t.flags & MF_SPHERE) return quadric_light_sample_li(quadric_of(sc, t), lt, ref, u, wi, pdf, ls);
+        return light_sample_li<F>(sc, lt, ref.p, u, wi, pdf, ls, &t);
+    }
+    return light_sample_li<F>(sc, lt, ref.p, u, wi, pdf, ls);
+}
+template <uint32_t F = 0xffffffffu>
+RDEV rgb light_power_ql(const SceneDev& sc, const rspt_light& lt) {
+    if (lt.kind == RSPT_LIGHT_DIFFUSE_AREA) {
+        const TriRec t = load_tri(sc, lt.prim);
+        if (t.flags & MF_SPHERE) return quadric_light_power(quadric_of(sc, t), lt);
+    }
+    return light_power<F>(sc, lt);
+}
 // One step of PathIntegrator::li (path.rs:91-280) for path slot p: fold in the previous
 // bounce's next-event estimate, then process the hit of the continuation ray.
 // F: the feature set the instantiation is compiled for (dev_bsdf.h SF_*): everything a scene outside F could bring folds away
 // MOVE (round 6, PathBuf::move): p is the path's POSITION in this iteration's queue; nothing the path carries on is stored here — it comes back in *mv and
 // shade_kernel stores it at the path's next position.  Indexed by the original slot `og` instead: the general form of a pending estimate.
 // SL: the scene holds a sphere area light (k_shade_sl only; a sphere set without MOVE form): the arms marked SL below, nothing else changes
-template <bool PIX, uint32_t F = SF_ALL, bool MOVE = false, bool SL = false>
+// QL: a scene with a disk or a cylinder holds an area light on a quadric (k_shade_ql only; a quadric set): the same arms over the slot's kind
+template <bool PIX, uint32_t F = SF_ALL, bool MOVE = false, bool SL = false, bool QL = false>
 RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const RenderDev& rd, const PathBuf& pb, uint32_t p, unsigned long long* stats,
                           const uint32_t* __restrict__ sob_tab, uint32_t sob_nd, PixSampler* px, ShadeMove* mv = nullptr) {
     ShadeOut out{false, false, false, false};
@@ -722,13 +744,15 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
                 TriRec t = load_tri(sc, hp);
                 if (t.area_light >= 0 && (uint32_t)t.area_light == light_num) {
                     Hit h;
-                    const bool mis_on_sphere = SL && (t.flags & MF_SPHERE) != 0;   // (false at compile time unless SL: the sphere arm below folds away)
+                    const bool mis_on_sphere = (SL || QL) && (t.flags & MF_SPHERE) != 0;   // (false at compile time unless SL / QL: the sphere arm below folds away)
                     if (!mis_on_sphere) tri_fill<(F & SF_VERTEX) != 0>(sc, hp, t, hm.y, hm.z, hm.w, &h);
                     const float4* mr = reinterpret_cast<const float4*>(pb.ray_mis + og);
                     float4 m0 = mr[0], m1 = mr[1];
                     f3 wi{m0.w, m1.x, m1.y};
                     // the MIS ray ended on the light's sphere: its interaction from the ray itself, with the ray's own t_max (see sphere_fill)
-                    if (mis_on_sphere) sphere_fill(sc, t, f3{m0.x, m0.y, m0.z}, wi, m1.z, &h, nullptr);
+                    // (QL: on the light's quadric, by the slot's kind: quadric_fill)
+                    if constexpr (QL) { if (mis_on_sphere) quadric_fill(sc, t, f3{m0.x, m0.y, m0.z}, wi, m1.z, &h, nullptr); }
+                    else if (mis_on_sphere) sphere_fill(sc, t, f3{m0.x, m0.y, m0.z}, wi, m1.z, &h, nullptr);
                     rgb li = light_l(sc.lights[light_num], h.n, -wi);
                     if (!is_black(li)) ldir = ldir + rgb{c2.x, c2.y, c2.z};
                 }
@@ -857,7 +881,8 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
                         float light_pdf = 0.0f, scattering_pdf = 0.0f;
                         LightSample ls;
                         rgb li;
-                        if constexpr (SL) li = light_sample_li_sl<F>(sc, lt, SlRef{h.p, h.p_err, h.n}, u_light, &wi, &light_pdf, &ls);   // (the reference point's p, p_error, n: sphere.rs:399-400)
+                        if constexpr (QL) li = light_sample_li_ql<F>(sc, lt, SlRef{h.p, h.p_err, h.n}, u_light, &wi, &light_pdf, &ls);   // (disk.rs:240-260, cylinder.rs:375-395)
+                        else if constexpr (SL) li = light_sample_li_sl<F>(sc, lt, SlRef{h.p, h.p_err, h.n}, u_light, &wi, &light_pdf, &ls);   // (the reference point's p, p_error, n: sphere.rs:399-400)
                         else li = light_sample_li<F>(sc, lt, h.p, u_light, &wi, &light_pdf, &ls);
                         if (light_pdf > 0.0f && !is_black(li)) {
                             rgb f = bsdf.template f<F>(wo, wi, nonspec) * mkrgb(absdot(wi, h.sh_n));
@@ -889,10 +914,12 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
                             // light's own sphere_test on that ray with t_max = infinity misses whenever the traversal's, under a smaller t_max, would (t_max only rejects): a miss
                             // here means no term, whatever the cone pdf says off the cone.  Nothing a miss would have computed is read afterwards.
                             bool sl_sphere = false;   // the light sits on a sphere; only ever set under SL, so every `if (sl_sphere)` below folds away in the other instantiations
-                            if constexpr (SL) sl_sphere = area_mis && (lt_tri.flags & MF_SPHERE) != 0;
+                            // QL: the same with the light's own disk_test / cylinder_test / sphere_test (quadric_test), which honour inner_radius, phi_max and the z clip
+                            if constexpr (SL || QL) sl_sphere = area_mis && (lt_tri.flags & MF_SPHERE) != 0;
                             rgb f = bsdf.template sample_f_if<F>(wo, &wi, u_scatter, &scattering_pdf, nonspec, &sampled_type, [&](f3 w) {
                                 if (!area_mis) return false;
-                                if (sl_sphere) { on_light = sphere_test(sphere_of(sc, lt_tri), offset_ray_origin(h.p, h.p_err, h.n, w), w, RSPT_INF, &t_l); return !on_light; }
+                                if constexpr (QL) { if (sl_sphere) { on_light = quadric_test(quadric_of(sc, lt_tri), offset_ray_origin(h.p, h.p_err, h.n, w), w, RSPT_INF, &t_l); return !on_light; } }
+                                else if (sl_sphere) { on_light = sphere_test(sphere_of(sc, lt_tri), offset_ray_origin(h.p, h.p_err, h.n, w), w, RSPT_INF, &t_l); return !on_light; }
                                 on_light = tri_test(lt_tri.p0, lt_tri.p1, lt_tri.p2, offset_ray_origin(h.p, h.p_err, h.n, w), ray_shear(w), RSPT_INF, &t_l, &lb0, &lb1, &lb2);
                                 return !on_light;
                             });
@@ -907,12 +934,14 @@ RDEVN ShadeOut shade_path(const SceneDev& sc, const LightDistDev& ld, const Rend
                                 } else {  // DiffuseAreaLight::pdf_li -> Triangle::pdf_with_ref_point (triangle.rs:745-764)
                                     if (!area_mis) {
                                         lt_tri = load_tri(sc, lt.prim);
-                                        if constexpr (SL) sl_sphere = (lt_tri.flags & MF_SPHERE) != 0;
-                                        if (sl_sphere) on_light = sphere_test(sphere_of(sc, lt_tri), ro, wi, RSPT_INF, &t_l);
+                                        if constexpr (SL || QL) sl_sphere = (lt_tri.flags & MF_SPHERE) != 0;
+                                        if (QL && sl_sphere) on_light = quadric_test(quadric_of(sc, lt_tri), ro, wi, RSPT_INF, &t_l);
+                                        else if (sl_sphere) on_light = sphere_test(sphere_of(sc, lt_tri), ro, wi, RSPT_INF, &t_l);
                                         else on_light = tri_test(lt_tri.p0, lt_tri.p1, lt_tri.p2, ro, ray_shear(wi), RSPT_INF, &t_l, &lb0, &lb1, &lb2);
                                     }
                                     if (sl_sphere) {   // DiffuseAreaLight::pdf_li -> Sphere::pdf_with_ref_point (sphere.rs:468-504); inf for a tiny far light is kept
-                                        if (on_light) lpdf = sphere_pdf_ref(sphere_of(sc, lt_tri), SlRef{h.p, h.p_err, h.n}, wi);
+                                        if constexpr (QL) { if (on_light) lpdf = quadric_pdf_ref(quadric_of(sc, lt_tri), SlRef{h.p, h.p_err, h.n}, wi); }   // (disk.rs:261-280, cylinder.rs:396-415)
+                                        else if (on_light) lpdf = sphere_pdf_ref(sphere_of(sc, lt_tri), SlRef{h.p, h.p_err, h.n}, wi);
                                     } else if (on_light) {
                                         Hit lh;
                                         tri_fill<(F & SF_VERTEX) != 0>(sc, lt.prim, lt_tri, lb0, lb1, lb2, &lh);
@@ -1290,7 +1319,7 @@ RSPT_PLAIN_KERNEL __launch_bounds__(256) void k_bin_scatter(const uint32_t* __re
 // to the compiler, k_shade_w<F, W> asks for W waves per SIMD (the allocator spills what does not fit 512 / W registers).
 // MOVE (round 6): queue entries are positions; what a path carries on is stored at its position in the next queue (PathBuf, ShadeMove)
 struct ShadeStage { float4 c1[256]; float4 sh0[256]; float2 sh1[256]; };   // 10 KB of LDS per workgroup (MOVE instantiations only)
-template <uint32_t F, bool MOVE, bool SL = false>
+template <uint32_t F, bool MOVE, bool SL = false, bool QL = false>
 __device__ __forceinline__ void shade_kernel(const SceneDev& sc, const LightDistDev& ld, const RenderDev& rd, const PathBuf& pb, const uint32_t* __restrict__ q_active,
                                              const QueueCounts* __restrict__ cnt_in, QueueCounts* cnt_out, uint32_t* __restrict__ q_active_next,
                                              uint32_t* __restrict__ q_closest_next, uint32_t* __restrict__ q_any_next, unsigned long long* stats,
@@ -1316,7 +1345,7 @@ __device__ __forceinline__ void shade_kernel(const SceneDev& sc, const LightDist
         uint32_t p = 0;
         if (i < n) {
             p = i < n_front ? (q_sorted ? q_sorted[i] : q_active[i]) : q_active[qcap - 1u - (i - n_front)];
-            if (p != RSPT_BIN_INVALID) o = shade_path<false, F, MOVE, SL>(sc, ld, rd, pb, p, stats, sob_tab, sob_nd, nullptr, MOVE ? &mv : nullptr);
+            if (p != RSPT_BIN_INVALID) o = shade_path<false, F, MOVE, SL, QL>(sc, ld, rd, pb, p, stats, sob_tab, sob_nd, nullptr, MOVE ? &mv : nullptr);
         }
         // queue appends, aggregated per workgroup: a single counter word sustains only ~90 M atomics/s
         // (MI355X_MICROARCH "dequeue" row), so one atomic per queue per 256 paths instead of per wave.
@@ -1410,6 +1439,14 @@ __global__ __launch_bounds__(256) void k_shade_sl(RSPT_SHADE_ARGS) {
     extern __shared__ uint32_t sob_tab[];
     __shared__ uint32_t s_wave[4][5], s_base[4];
     shade_kernel<F, false, true>(sc, ld, rd, pb, q_active, cnt_in, cnt_out, q_active_next, q_closest_next, q_any_next, stats, sob_nd, sob_bits, qcap, q_sorted, bi, sob_tab, s_wave, s_base, nullptr);
+}
+// The quadric-light builds (rspt_set_quadric_lights): a quadric set's body with the same arms over the slot's kind (QL), again under a name of its own.
+// No MOVE form, no fast-math form.
+template <uint32_t F>
+__global__ __launch_bounds__(256) void k_shade_ql(RSPT_SHADE_ARGS) {
+    extern __shared__ uint32_t sob_tab[];
+    __shared__ uint32_t s_wave[4][5], s_base[4];
+    shade_kernel<F, false, false, true>(sc, ld, rd, pb, q_active, cnt_in, cnt_out, q_active_next, q_closest_next, q_any_next, stats, sob_nd, sob_bits, qcap, q_sorted, bi, sob_tab, s_wave, s_base, nullptr);
 }
 // the MOVE forms (W = 0: the compiler's own register budget)
 template <uint32_t F, int W>
@@ -1802,8 +1839,9 @@ RDEV float radical_inverse(int base_index, uint64_t a) {  // lowdiscrepancy.rs:1
     }
     return fminf((float)reversed * inv_base_n, RSPT_ONE_MINUS_EPS);
 }
-// SpatialLightDistribution::compute_distribution, per (voxel, light) (lightdistrib.rs:169-260); F as in light_sample_li; SL: the scene holds a sphere area light
-template <uint32_t F = 0xffffffffu, bool SL = false>
+// SpatialLightDistribution::compute_distribution, per (voxel, light) (lightdistrib.rs:169-260); F as in light_sample_li; SL: the scene holds a sphere area light;
+// QL: a scene with a disk or a cylinder holds an area light on a quadric
+template <uint32_t F = 0xffffffffu, bool SL = false, bool QL = false>
 RDEV float ld_voxel_light_contrib(const SceneDev& sc, int32_t nvx, int32_t nvy, int32_t nvz, uint64_t v, uint32_t j) {
     int32_t ix = (int32_t)(v % nvx), iy = (int32_t)((v / nvx) % nvy), iz = (int32_t)(v / ((uint64_t)nvx * nvy));
     f3 wmin{sc.wb_min[0], sc.wb_min[1], sc.wb_min[2]}, wmax{sc.wb_max[0], sc.wb_max[1], sc.wb_max[2]};
@@ -1821,7 +1859,8 @@ RDEV float ld_voxel_light_contrib(const SceneDev& sc, int32_t nvx, int32_t nvy, 
         f3 wi{0.0f, 0.0f, 0.0f};
         LightSample ls;
         rgb li;
-        if constexpr (SL) li = light_sample_li_sl<F>(sc, lt, SlRef{po, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}}, u, &wi, &pdf, &ls);   // a bare point: p_error = n = 0 (lightdistrib.rs:215-222)
+        if constexpr (QL) li = light_sample_li_ql<F>(sc, lt, SlRef{po, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}}, u, &wi, &pdf, &ls);
+        else if constexpr (SL) li = light_sample_li_sl<F>(sc, lt, SlRef{po, f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 0.0f}}, u, &wi, &pdf, &ls);   // a bare point: p_error = n = 0 (lightdistrib.rs:215-222)
         else li = light_sample_li<F>(sc, lt, po, u, &wi, &pdf, &ls);
         if (pdf > 0.0f) contrib += lum(li) / pdf;
     }
@@ -1859,6 +1898,19 @@ RSPT_PLAIN_KERNEL void k_ld_fixed_sl(SceneDev sc, int power, float* __restrict__
     if (j >= sc.n_lights) return;
     if (!power) { func[j] = 1.0f; return; }
     func[j] = lum(light_power_sl(sc, sc.lights[j]));
+}
+// ... and over a scene with a disk or a cylinder that holds an area light on a quadric, served while the quadric-light gate is on (rspt_set_quadric_lights)
+RSPT_PLAIN_KERNEL void k_ld_contrib_ql(SceneDev sc, int32_t nvx, int32_t nvy, int32_t nvz, float* __restrict__ func) {
+    uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t total = (uint64_t)nvx * nvy * nvz * sc.n_lights;
+    if (gid >= total) return;
+    func[gid] = ld_voxel_light_contrib<0xffffffffu, false, true>(sc, nvx, nvy, nvz, gid / sc.n_lights, (uint32_t)(gid % sc.n_lights));
+}
+RSPT_PLAIN_KERNEL void k_ld_fixed_ql(SceneDev sc, int power, float* __restrict__ func) {
+    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= sc.n_lights) return;
+    if (!power) { func[j] = 1.0f; return; }
+    func[j] = lum(light_power_ql(sc, sc.lights[j]));
 }
 // one Distribution1D per voxel (sampling.rs:24-49) after the min-contribution clamp (:262-268);
 // mode 0: spatial (func holds raw contributions), 1: use func as is (uniform / power)

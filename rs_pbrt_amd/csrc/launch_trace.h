@@ -282,7 +282,8 @@ typedef void (*ShadeKernel)(RSPT_SHADE_ARGS);
 // 4 waves 455; plastic 173 VGPRs as compiled 1749 (0.531 s), 168 + 24 B of spills = 3 waves 1841 (0.470 s), 128 + 152 B = 4 waves 1791.
 struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, w3, w4; int dflt; ShadeKernel move; /* the MOVE form (kernels.h PathBuf::move), built as this set's default is; nullptr: none */
                       ShadeKernel f_natural, f_w3, f_w4, f_move; /* the fast-math builds of the same four (kernels.h k_shade_fast*, the SHADE_F* groups of tu_decl.h); nullptr: the set has none */
-                      bool sphere_lights; /* the set carries the sphere-light arms (kernels.h k_shade_sl): taken by a sphere scene with an emissive sphere, and by nothing else */ };
+                      bool sphere_lights; /* the set carries the sphere-light arms (kernels.h k_shade_sl): taken by a sphere scene with an emissive sphere, and by nothing else */
+                      bool quadric_lights; /* the set carries the quadric-light arms (kernels.h k_shade_ql): taken by a scene with a disk or a cylinder that serves an area light on a quadric, and by nothing else */ };
 // A row names its set once.  _W: a set run at 3 waves by default, its MOVE form built so; W4 = the build behind w4 (the Halton sets have none for 4 waves: 3 again).
 // _N: a set run as compiled, its MOVE form too.  Both with their fast-math twins.  _PLAIN: one build, no MOVE form, no fast twins.
 #define RSPT_SV_ROW_W(F, NAME, W4) \
@@ -290,6 +291,7 @@ struct ShadeVariant { uint32_t features; const char* name; ShadeKernel natural, 
 #define RSPT_SV_ROW_N(F, NAME) {F, NAME, k_shade<F>, k_shade_w<F, 3>, k_shade_w<F, 4>, 0, k_shade_m<F>, k_shade_fast<F>, k_shade_fast_w<F, 3>, k_shade_fast_w<F, 4>, k_shade_fast_m<F>}
 #define RSPT_SV_ROW_PLAIN(F, NAME) {F, NAME, k_shade<F>, k_shade<F>, k_shade<F>, 0, nullptr}
 #define RSPT_SV_ROW_SL(F, NAME) {F, NAME, k_shade_sl<F>, k_shade_sl<F>, k_shade_sl<F>, 0, nullptr, nullptr, nullptr, nullptr, nullptr, true}
+#define RSPT_SV_ROW_QL(F, NAME) {F, NAME, k_shade_ql<F>, k_shade_ql<F>, k_shade_ql<F>, 0, nullptr, nullptr, nullptr, nullptr, nullptr, false, true}
 const ShadeVariant g_shade_variants[] = {
     RSPT_SV_ROW_W(SV_DIFFUSE, "diffuse", 4),   // (round 4: as compiled it now takes 169 VGPRs = 2 waves — the in-kernel voxel claim of light_row_try
                                                //  cost the four registers; the 3-wave build fits 168 without scratch: Cornell 875 -> see profiles/r04_*)
@@ -317,6 +319,12 @@ const ShadeVariant g_shade_variants[] = {
     // that scene's spheres and triangles too.  Only such scenes take them and such scenes take nothing else.  Figures: DESIGN section 5.1b.
     RSPT_SV_ROW_PLAIN(SV_GENERIC_QUAD, "generic-quadric"),
     RSPT_SV_ROW_PLAIN(SV_DYNAMIC_QUAD, "dynamic-quadric"),
+    // such scenes that hold an emissive disk, cylinder or sphere, while the quadric-light gate is on (rspt_set_quadric_lights; an emissive sphere there needs
+    // the sphere-light gate too): the same two feature sets with the quadric-light arms of shade_path (DiffuseAreaLight over the sample_with_ref_point /
+    // pdf_with_ref_point of the slot's kind, dev_quadric_light.h).  Only such renders take them and such renders take nothing else.  No MOVE form, no
+    // fast-math form: they run exact under either shade-math mode.  Figures: DESIGN section 5.1b.
+    RSPT_SV_ROW_QL(SV_GENERIC_QUAD, "generic-quadriclight"),
+    RSPT_SV_ROW_QL(SV_DYNAMIC_QUAD, "dynamic-quadriclight"),
     // scenes with a projection or goniometric light (ABI 24, SF_L_MAP; Sobol' and Halton): the generic and the all-features set with the two arms of
     // light_sample_li / light_is_delta (dev_bsdf.h shade_ml).  Only such scenes take them and such scenes take nothing else.  No MOVE form: the
     // schedule was left off for them (unmeasured there), they keep slots for life.
@@ -328,13 +336,16 @@ const ShadeVariant g_shade_variants[] = {
 // fast (rspt_set_shade_math / RSPT_SHADE_MATH, resolved by the caller): the fast-math builds of the chosen set, picked by the same switches, where the set has them;
 // *fast_out then says so.  A set without them (dynamic, moving, sphere, quadric, map-light) is served by its exact kernels: a mode that permits approximation may be exact.
 // sphere_lights: the render serves a sphere area light (the caller has checked the gate): only the sets that carry those arms, and they for nothing else
-ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr, bool fast = false, bool* fast_out = nullptr, bool sphere_lights = false) {
+// quadric_lights: the render serves an area light on a quadric in a scene with a disk or a cylinder (the caller has checked the gates): likewise
+ShadeKernel shade_kernel_for(uint32_t need, const char** name_out, ShadeKernel* move_out = nullptr, bool fast = false, bool* fast_out = nullptr, bool sphere_lights = false,
+                             bool quadric_lights = false) {
     const char* force = getenv("RSPT_SHADE_VARIANT");
     if (move_out) *move_out = nullptr;
     if (fast_out) *fast_out = false;
     const bool sph = (need & SF_SPHERE) != 0, ml = (need & SF_L_MAP) != 0, quad = (need & SF_QUADRIC) != 0;
     for (const ShadeVariant& v : g_shade_variants) {
         if (v.sphere_lights != sphere_lights) continue;
+        if (v.quadric_lights != quadric_lights) continue;
         if (shade_sph(v.features) != sph) continue;   // (the triangle sets carry the SF_SPHERE bit too, without the arm: see dev_bsdf.h SF_TRIS_ONLY)
         if (shade_quad(v.features) != quad) continue; // (... and SF_QUADRIC: SF_NO_QUADRIC; a quadric scene's need carries SF_SPHERE too)
         if (shade_ml(v.features) != ml) continue;     // (... and SF_L_MAP: SF_NO_MAPLIGHT)

@@ -518,8 +518,21 @@ int sphere_lights_mode() {
     if (!strcmp(e, "1")) return 1;
     return -1;
 }
+// ---- the quadric-light gate (include/rspt.h rspt_set_quadric_lights): the same for disk and cylinder area lights ----
+std::atomic<uint32_t> g_quadric_lights{0u};
+int quadric_lights_mode() {
+    const char* e = getenv("RSPT_QUADRIC_LIGHTS");
+    if (!e || !*e) return (int)g_quadric_lights.load();
+    if (!strcmp(e, "0")) return 0;
+    if (!strcmp(e, "1")) return 1;
+    return -1;
+}
+// the area lights on quadrics that a scene with a disk or a cylinder holds, for the refusals of a call that serves them: "disk area lights", .. or, where only
+// a sphere emits there, "sphere area lights"
+const char* quadric_scene_lights_what(const rspt_scene_s* s) { return s->quadric_light_kinds ? s->quadric_light_what : "sphere area lights"; }
 
 // Light distribution for (scene, strategy): create_light_sample_distribution (lightdistrib.rs:393-418)
+// (a scene with a disk or a cylinder that holds an emissive quadric reaches this only while the gates its lights need are on: the _ql kernels build its tables)
 // (a scene with an emissive sphere reaches this only while the sphere-light gate is on: its tables come from the kernels that carry the sphere arm)
 int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const LightDist** lazy_out = nullptr) {
     const uint32_t nl = s->dev.n_lights;
@@ -527,6 +540,7 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
     out->nvox[0] = out->nvox[1] = out->nvox[2] = 1;
     if (nl == 0) return RSPT_OK;
     int eff = (strategy == RSPT_LIGHTS_UNIFORM || nl == 1) ? RSPT_LIGHTS_UNIFORM : (strategy == RSPT_LIGHTS_POWER ? RSPT_LIGHTS_POWER : RSPT_LIGHTS_SPATIAL);
+    const bool ql = s->has_quadrics && (s->quadric_light_kinds || s->has_sphere_light);   // an area light on a quadric in a scene whose slots are QuadricDev
     auto it = s->light_dists.find(eff);
     if (it == s->light_dists.end()) {
         LightDist d;
@@ -553,6 +567,7 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             if (lazy) n_rows = std::max<uint64_t>(1, std::min<uint64_t>(n_vox, env_size("RSPT_LIGHT_TABLE_POOL_BYTES", (size_t)16 << 30) / row_bytes));
             // (the on-demand kernels carry no projection / goniometric arm: such a scene takes the table built up front or nothing)
             if (lazy && s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES)", s->maplight_kinds);
+            if (lazy && ql && s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES): the on-demand kernels carry no %s", s->quadric_light_kinds, s->quadric_light_what);
             if (lazy && s->has_sphere_light) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere whose spatial light table needs on-demand voxels (more than RSPT_LIGHT_TABLE_EAGER_BYTES): the on-demand kernels carry no sphere area light");
             if (n_rows > 0x7fffffffull || n_vox > 0x7fffffffull) return fail(RSPT_E_UNSUPPORTED, "spatial light distribution: %llu voxels", (unsigned long long)n_vox);
         }
@@ -568,10 +583,10 @@ int get_light_dist(rspt_scene_s* s, uint32_t strategy, LightDistDev* out, const 
             HIP_TRY(hipMemcpyAsync(d.lazy, &lz, sizeof lz, hipMemcpyHostToDevice, g.stream));
         } else if (eff == RSPT_LIGHTS_SPATIAL) {
             uint64_t total = n_vox * nl;
-            hipLaunchKernelGGL(s->has_sphere_light ? k_ld_contrib_sl : s->has_maplights ? k_ld_contrib_ml : k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
+            hipLaunchKernelGGL(ql ? k_ld_contrib_ql : s->has_sphere_light ? k_ld_contrib_sl : s->has_maplights ? k_ld_contrib_ml : k_ld_contrib, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, g.stream, s->dev, d.nvox[0], d.nvox[1], d.nvox[2], d.func);
             hipLaunchKernelGGL(k_ld_build, dim3((uint32_t)((n_vox + 255) / 256)), dim3(256), 0, g.stream, (uint32_t)n_vox, nl, 0, d.func, d.cdf, d.func_int);
         } else {
-            hipLaunchKernelGGL(s->has_sphere_light ? k_ld_fixed_sl : s->has_maplights ? k_ld_fixed_ml : k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
+            hipLaunchKernelGGL(ql ? k_ld_fixed_ql : s->has_sphere_light ? k_ld_fixed_sl : s->has_maplights ? k_ld_fixed_ml : k_ld_fixed, dim3((nl + 255) / 256), dim3(256), 0, g.stream, s->dev, eff == RSPT_LIGHTS_POWER ? 1 : 0, d.func);
             hipLaunchKernelGGL(k_ld_build, dim3(1), dim3(64), 0, g.stream, 1u, nl, 1, d.func, d.cdf, d.func_int);
         }
         HIP_TRY(hipGetLastError());
@@ -776,6 +791,13 @@ int rspt_set_sphere_lights(uint32_t on) {
     return RSPT_OK;
 }
 int rspt_get_sphere_lights(void) { return (int)g_sphere_lights.load(); }
+// the quadric-light gate: the same (quadric_lights_mode above)
+int rspt_set_quadric_lights(uint32_t on) {
+    if (on > 1u) return fail(RSPT_E_INVALID, "quadric_lights = %u: 0 (off, the default) or 1 (on)", on);
+    g_quadric_lights.store(on);
+    return RSPT_OK;
+}
+int rspt_get_quadric_lights(void) { return (int)g_quadric_lights.load(); }
 // Replaces: BVHAccel::new (bvh.rs:96-392), on the device; see bvh_device.h
 int64_t rspt_bvh_build_gpu(const float* P, uint64_t n_vertices, const uint32_t* tri_idx, uint64_t n_tris, uint32_t max_prims_in_node,
                            rspt_bvh_node* nodes_out, uint64_t nodes_cap, uint32_t* ordered_out) {
@@ -1345,8 +1367,63 @@ __global__ void k_sphere_light(const float* __restrict__ x, uint64_t n, float* _
     r[21] = li.r; r[22] = li.g; r[23] = li.b; r[24] = wi.x; r[25] = wi.y; r[26] = wi.z; r[27] = pdf;
     r[28] = sphere_pdf_ref(sp, ref, wq);
 }
+// rspt_quadric_light: one rspt_disk or rspt_cylinder (40 words), its kind (the BITS of RSPT_MESH_DISK / RSPT_MESH_CYLINDER), a flags word (non-zero: two-sided),
+// the reference point's p, p_error, n, u[2] and a query direction wi -> area / sample / sample_with_ref_point / pdf_with_ref_point of the shape and
+// DiffuseAreaLight::sample_li / power of L = 1 (dev_quadric_light.h); 64 floats in and out.  Any other kind: all words 0.
+__global__ void k_quadric_light(const float* __restrict__ x, uint64_t n, float* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    QuadricDev qd;
+    uint32_t* qw = reinterpret_cast<uint32_t*>(&qd);
+    for (int k = 0; k < (int)(sizeof(QuadricDev) / 4); k++) qw[k] = 0u;
+    for (int k = 0; k < 40; k++) qw[k] = __float_as_uint(x[64 * i + k]);
+    const uint32_t kind = __float_as_uint(x[64 * i + 40]);
+    qd.kind = kind == RSPT_MESH_DISK ? QK_DISK : QK_CYLINDER;
+    const float* q = x + 64 * i + 42;
+    rspt_light lt{};
+    lt.kind = RSPT_LIGHT_DIFFUSE_AREA;
+    lt.L[0] = lt.L[1] = lt.L[2] = 1.0f;
+    lt.two_sided = __float_as_uint(q[0]) != 0u;
+    const SlRef ref{f3{q[1], q[2], q[3]}, f3{q[4], q[5], q[6]}, f3{q[7], q[8], q[9]}};
+    const f2 u{q[10], q[11]};
+    const f3 wq{q[12], q[13], q[14]};
+    float* r = out + 64 * i;
+    for (int k = 0; k < 64; k++) r[k] = 0.0f;
+    if (kind != RSPT_MESH_DISK && kind != RSPT_MESH_CYLINDER) return;
+    r[0] = quadric_area(qd);
+    float pdf = 0.0f;
+    LightSample a = quadric_sample(qd, u, &pdf);
+    r[1] = a.p.x; r[2] = a.p.y; r[3] = a.p.z; r[4] = a.p_err.x; r[5] = a.p_err.y; r[6] = a.p_err.z; r[7] = a.n.x; r[8] = a.n.y; r[9] = a.n.z; r[10] = pdf;
+    pdf = 0.0f;
+    a = quadric_sample_ref(qd, ref, u, &pdf);
+    r[11] = a.p.x; r[12] = a.p.y; r[13] = a.p.z; r[14] = a.p_err.x; r[15] = a.p_err.y; r[16] = a.p_err.z; r[17] = a.n.x; r[18] = a.n.y; r[19] = a.n.z; r[20] = pdf;
+    pdf = 0.0f;
+    f3 wi{0.0f, 0.0f, 0.0f};
+    const rgb li = quadric_light_sample_li(qd, lt, ref, u, &wi, &pdf, &a);
+    r[21] = li.r; r[22] = li.g; r[23] = li.b; r[24] = wi.x; r[25] = wi.y; r[26] = wi.z; r[27] = pdf;
+    r[28] = quadric_pdf_ref(qd, ref, wq);
+    const rgb pw = quadric_light_power(qd, lt);
+    r[29] = pw.r; r[30] = pw.g; r[31] = pw.b;
+}
 }  // namespace
 extern "C" {
+int rspt_quadric_light(const float* x, uint64_t n, float* out) {
+    if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
+    if (n == 0) return RSPT_OK;
+    if (!x || !out || n > (1ull << 25)) return fail(RSPT_E_INVALID, "null argument or more than 2^25 elements");
+    HIP_TRY(hipSetDevice(g.device));
+    float *xd = nullptr, *od = nullptr;
+    struct Guard { float **a, **b; ~Guard() { for (float** p : {a, b}) if (*p) (void)hipFree(*p); } } guard{&xd, &od};
+    int rc;
+    if ((rc = dev_alloc(&xd, n * 64)) || (rc = dev_alloc(&od, n * 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(xd, x, n * 64 * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    hipLaunchKernelGGL(k_quadric_light, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, g.stream, xd, n, od);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, od, n * 64 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return RSPT_OK;
+}
+
 int rspt_sphere_light(const float* x, uint64_t n, float* out) {
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (n == 0) return RSPT_OK;
@@ -1409,7 +1486,23 @@ int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3],
     if (!g.inited) return fail(RSPT_E_NODEVICE, "rspt_init has not been called");
     if (!s || !p || !func_out || !cdf_out) return fail(RSPT_E_INVALID, "null argument");
     // (a scene whose spheres are no lights needs no sphere code here: the spatial voxels take the world bound from the BVH root, which holds the spheres)
-    if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: the light distributions are not built for %s yet", s->quadric_light_kinds, s->quadric_light_what);
+    bool ql_on = false;
+    if (s->quadric_light_kinds) {   // served while the quadric-light gate is on (rspt_set_quadric_lights) by the _ql kernels; off: today's answer
+        const int ql = quadric_lights_mode();
+        if (ql < 0) return fail(RSPT_E_INVALID, "RSPT_QUADRIC_LIGHTS=%s: 0 or 1", getenv("RSPT_QUADRIC_LIGHTS"));
+        if (!ql) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: the light distributions are not built for %s yet", s->quadric_light_kinds, s->quadric_light_what);
+        ql_on = true;
+    }
+    if (s->has_sphere_light && s->has_quadrics) {   // an emissive sphere in a scene with a disk or a cylinder: served by the _ql kernels while BOTH gates are on
+        const int sl = sphere_lights_mode();
+        if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
+        const int ql = ql_on ? 1 : quadric_lights_mode();
+        if (!sl && ql == 1) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: a sphere area light there needs the sphere-light gate too (rspt_set_sphere_lights)", s->quadric_kinds);
+        if (!sl) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere: the light distributions are not built for sphere area lights yet");
+        if (ql < 0) return fail(RSPT_E_INVALID, "RSPT_QUADRIC_LIGHTS=%s: 0 or 1", getenv("RSPT_QUADRIC_LIGHTS"));
+        if (!ql) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: the sphere area light kernels read sphere records only", s->quadric_kinds);
+        ql_on = true;
+    } else
     if (s->has_sphere_light) {   // served while the sphere-light gate is on (rspt_set_sphere_lights), for a sphere scene the _sl kernels cover; off: today's answer
         const int sl = sphere_lights_mode();
         if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
@@ -1417,6 +1510,7 @@ int rspt_light_distribution(rspt_scene_t s, uint32_t strategy, const float p[3],
         if (s->has_quadrics) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: the sphere area light kernels read sphere records only", s->quadric_kinds);
         if (s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s light: the sphere area light kernels carry no map light", s->maplight_kinds);
     }
+    if (ql_on && s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with %s next to a %s light: the quadric area light kernels carry no map light", quadric_scene_lights_what(s), s->maplight_kinds);
     // (a scene with projection / goniometric lights: get_light_dist launches the kernels that carry their arms, and refuses the on-demand table)
     const uint32_t nl = s->dev.n_lights;
     if (nl == 0) return fail(RSPT_E_INVALID, "the scene has no lights");

@@ -30,6 +30,7 @@ struct RenderRun {
     bool counters = false, ao = false, dl_lane = false, dl_one_round = false, move = false;
     const char* shade_name = "generic"; ShadeKernel shade_k = nullptr, shade_move_k = nullptr;
     bool sphere_lights = false;   // validate(): the scene holds an emissive sphere and the sphere-light gate is on (rspt_set_sphere_lights): the sphere-light shade sets serve it
+    bool quadric_lights = false;  // validate(): a scene with a disk or a cylinder holds an area light on a quadric and the gates it needs are on (rspt_set_quadric_lights): the quadric-light shade sets serve it
     int shade_math = RSPT_SHADE_MATH_EXACT; bool shade_fast = false; char shade_name_fast[48];   // validate(): the mode; size_batches(): whether fast builds serve this render (then shade_name = "<set>-fast")
     // prepare(): the per-lane directlighting forms' arrays, iteration counts, launch geometry, events (kev: per-launch durations, each pair recorded on the
     // stream its kernel runs on — closest-hit, shadow-ray, shade [+ texture])
@@ -114,12 +115,37 @@ int RenderRun::validate() {
         static const char* const names[] = {"path", "ao", "directlighting", "volpath", "whitted"};
         const char* iname = d->integrator < 5 ? names[d->integrator] : "?";
         const char* q = s->quadric_kinds;
-        if (s->quadric_light_kinds) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: %s are not served on the device yet (%s)", s->quadric_light_kinds, s->quadric_light_what, iname);
+        // In such a scene a shape's area light is served only while that shape's gate is on: an emissive disk or cylinder needs the quadric-light gate
+        // (rspt_set_quadric_lights), an emissive sphere both gates.  With the quadric gate off every answer below is the one from before that gate existed.
+        if (s->quadric_light_kinds) {
+            const int ql = quadric_lights_mode();
+            if (ql < 0) return fail(RSPT_E_INVALID, "RSPT_QUADRIC_LIGHTS=%s: 0 or 1", getenv("RSPT_QUADRIC_LIGHTS"));
+            if (!ql) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive %s: %s are not served on the device yet (%s)", s->quadric_light_kinds, s->quadric_light_what, iname);
+            quadric_lights = true;
+        }
         if (s->has_sphere_light) {
-            const int sl = sphere_lights_mode();   // the gate (rspt_set_sphere_lights): off, today's answer; on, still refused: the sphere-light kernels read sphere records only
+            const int sl = sphere_lights_mode();   // the gate (rspt_set_sphere_lights)
             if (sl < 0) return fail(RSPT_E_INVALID, "RSPT_SPHERE_LIGHTS=%s: 0 or 1", getenv("RSPT_SPHERE_LIGHTS"));
+            const int ql = quadric_lights ? 1 : quadric_lights_mode();
+            if (!sl && ql == 1) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: a sphere area light there needs the sphere-light gate too (rspt_set_sphere_lights) (%s)", q, iname);
             if (!sl) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are not served on the device yet (%s)", q, iname);
-            return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are served in scenes without a disk or a cylinder only (%s)", q, iname);
+            if (ql < 0) return fail(RSPT_E_INVALID, "RSPT_QUADRIC_LIGHTS=%s: 0 or 1", getenv("RSPT_QUADRIC_LIGHTS"));
+            if (!ql) return fail(RSPT_E_UNSUPPORTED, "scene with an emissive sphere next to a %s: sphere area lights are served in scenes without a disk or a cylinder only (%s)", q, iname);
+            quadric_lights = true;
+        }
+        if (quadric_lights) {
+            // Served by path under Sobol' / Halton (the quadric-light shade sets, launch_trace.h) and by ao, which reads no lights; everything else is refused by
+            // name ("disk area light" / "cylinder area light"; "sphere area light" where only a sphere emits), so the caller keeps its CPU loop.
+            const char* what = quadric_scene_lights_what(s);
+            if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
+                return fail(RSPT_E_UNSUPPORTED, "scene with %s under the %s integrator: these lights are served by path (and ao, which reads no lights) only", what, iname);
+            if (d->sampler_kind != RSPT_SAMPLER_SOBOL && d->sampler_kind != RSPT_SAMPLER_HALTON)
+                return fail(RSPT_E_UNSUPPORTED, "scene with %s under the %s sampler: these lights are served with the sobol and halton samplers only", what,
+                            d->sampler_kind == RSPT_SAMPLER_RANDOM ? "random" : d->sampler_kind == RSPT_SAMPLER_ZEROTWO ? "02sequence" : d->sampler_kind == RSPT_SAMPLER_STRATIFIED ? "stratified" :
+                            d->sampler_kind == RSPT_SAMPLER_MAXMINDIST ? "maxmindist" : "unknown");
+            if (!s->w4_ok) return fail(RSPT_E_UNSUPPORTED, "scene with %s and more four-box records than a reference holds", what);
+            if (env_size("RSPT_COUNTERS", 0) != 0) return fail(RSPT_E_UNSUPPORTED, "RSPT_COUNTERS on a scene with %s: the quadric traversal keeps no node counters", what);
+            if (s->has_maplights) return fail(RSPT_E_UNSUPPORTED, "scene with a %s light next to %s: that pair has no shade instantiation", s->maplight_kinds, what);
         }
         if (d->integrator != RSPT_INTEGRATOR_PATH && d->integrator != RSPT_INTEGRATOR_AO)
             return fail(RSPT_E_UNSUPPORTED, "scene with a %s under the %s integrator: these shapes are served by path and ao only", q, iname);
@@ -456,9 +482,10 @@ int RenderRun::size_batches() {
     // the fast-math builds (rspt_set_shade_math): the path integrator's wavefront form under Sobol' / Halton only, and only the sets that have them; every other render
     // of a fast-mode process runs the exact kernels under the plain name
     const bool want_fast = shade_math == RSPT_SHADE_MATH_FAST && d->integrator == RSPT_INTEGRATOR_PATH && !pixel_sampler;
-    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k, want_fast && !sphere_lights, &shade_fast, sphere_lights);
+    shade_k = shade_kernel_for(s->shade_features | (halton ? (uint32_t)SF_HALTON : (uint32_t)SF_SOBOL), &shade_name, &shade_move_k, want_fast && !sphere_lights && !quadric_lights, &shade_fast, sphere_lights, quadric_lights);
     if (shade_k && shade_fast) { snprintf(shade_name_fast, sizeof shade_name_fast, "%s-fast", shade_name); shade_name = shade_name_fast; }
     if (!shade_k) return fail(RSPT_E_UNSUPPORTED, s->has_maplights ? "RSPT_SHADE_VARIANT names no instantiation with the projection / goniometric arms (generic-maplight, all-maplight)"
+                                                                  : quadric_lights ? "RSPT_SHADE_VARIANT names no instantiation with the disk / cylinder area light arms (generic-quadriclight, dynamic-quadriclight)"
                                                                   : s->has_quadrics ? "RSPT_SHADE_VARIANT names no instantiation with the disk / cylinder arm (generic-quadric, dynamic-quadric)"
                                                                   : sphere_lights ? "RSPT_SHADE_VARIANT names no instantiation with the sphere area light arms (generic-spherelight, dynamic-spherelight)"
                                                                   : "RSPT_SHADE_VARIANT names no instantiation with the sphere arm (generic-sphere, dynamic-sphere)");

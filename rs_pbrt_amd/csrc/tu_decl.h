@@ -212,6 +212,15 @@ RSPT_TU_SHADE(, SV_GENERIC_QUAD)   /* scenes with a disk or a cylinder; no MOVE 
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_QD)
 RSPT_TU_SHADE(, SV_DYNAMIC_QUAD)
 #endif
+// scenes with a disk or a cylinder that hold an area light on a quadric, served while the quadric-light gate is on (rspt_set_quadric_lights): the two quadric
+// sets with the quadric-light arms of shade_path (kernels.h k_shade_ql); every kernel above keeps its name and its code
+#define RSPT_TU_SHADE_QL(F) RSPT_TU_X template __global__ void k_shade_ql<F>(RSPT_SHADE_ARGS);
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_QL)
+RSPT_TU_SHADE_QL(SV_GENERIC_QUAD)   /* no MOVE form, no fast-math form */
+#endif
+#if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_QLD)
+RSPT_TU_SHADE_QL(SV_DYNAMIC_QUAD)
+#endif
 #if defined(RSPT_TU_ALL) || defined(RSPT_TU_GROUP_SHADE_L)
 RSPT_TU_SHADE(, SV_GENERIC_ML) RSPT_TU_SHADE(, SV_ALL_ML)   /* scenes with projection / goniometric lights; no MOVE form */
 #endif

@@ -18,7 +18,8 @@ EXPORTS = ("rspt_abi_version", "rspt_init", "rspt_shutdown", "rspt_scene_create"
            "rspt_bvh_build_gpu", "rspt_bvh_build_bounds", "rspt_comm_unique_id", "rspt_comm_init", "rspt_comm_destroy", "rspt_light_distribution", "rspt_libm",
            "rspt_material_lobes", "rspt_camera_decompose", "rspt_motion_bounds", "rspt_source_hash", "rspt_comm_library", "rspt_realistic_camera_setup",
            "rspt_camera_rays", "rspt_quadric_intersect", "rspt_set_shade_math", "rspt_get_shade_math",
-           "rspt_set_sphere_lights", "rspt_get_sphere_lights", "rspt_sphere_light")
+           "rspt_set_sphere_lights", "rspt_get_sphere_lights", "rspt_sphere_light",
+           "rspt_set_quadric_lights", "rspt_get_quadric_lights", "rspt_quadric_light")
 
 
 def tree_source_hash():
@@ -97,6 +98,9 @@ def lib():
         L.rspt_set_sphere_lights.argtypes = [u32]
         L.rspt_get_sphere_lights.restype = C.c_int
         L.rspt_sphere_light.argtypes = [vp, u64, vp]
+        L.rspt_set_quadric_lights.argtypes = [u32]
+        L.rspt_get_quadric_lights.restype = C.c_int
+        L.rspt_quadric_light.argtypes = [vp, u64, vp]
         _LIB = L
     return _LIB
 
@@ -149,6 +153,40 @@ def sphere_light_pack(spheres, two_sided, ref_p, ref_p_error, ref_n, u, wi):
     x = np.zeros((n, 64), np.float32)
     x[:, :42] = np.ascontiguousarray(spheres).view(np.float32).reshape(n, 42)
     x[:, 42:43].view(np.uint32)[:, 0] = np.asarray(two_sided, bool).astype(np.uint32)
+    x[:, 43:46], x[:, 46:49], x[:, 49:52], x[:, 52:54], x[:, 54:57] = ref_p, ref_p_error, ref_n, u, wi
+    return x
+
+
+def set_quadric_lights(on):
+    """rspt_set_quadric_lights: True serves scenes with an emissive disk or cylinder where include/rspt.h says so (off by default: such a scene is refused).
+    Process-wide, host only; an integer is passed through as it is, so that a value above 1 meets the library's own refusal."""
+    _check(lib().rspt_set_quadric_lights(int(on)))
+
+
+def get_quadric_lights():
+    """what set_quadric_lights last set (the environment's RSPT_QUADRIC_LIGHTS, which overrides it per call, is not reflected)"""
+    return bool(lib().rspt_get_quadric_lights())
+
+
+def quadric_light(records, two_sided, ref_p, ref_p_error, ref_n, u, wi):
+    """rspt_quadric_light: records of DISK_DT or of CYLINDER_DT, per element a two-sided flag, the reference point (p, p_error, n), u (n, 2) and a query
+    direction -> (n, 64) f32: [0] area, [1:11] sample's p, p_error, n, pdf, [11:21] sample_with_ref_point's, [21:28] DiffuseAreaLight::sample_li's radiance of
+    L = 1, wi, pdf, [28] pdf_with_ref_point(ref, wi), [29:32] the power of L = 1.  Compare results as uint32 words."""
+    x = quadric_light_pack(records, two_sided, ref_p, ref_p_error, ref_n, u, wi)
+    out = np.empty_like(x)
+    _check(lib().rspt_quadric_light(x.ctypes.data, len(x), out.ctypes.data))
+    return out
+
+
+def quadric_light_pack(records, two_sided, ref_p, ref_p_error, ref_n, u, wi):
+    """the (n, 64) f32 input elements of rspt_quadric_light (include/rspt.h gives the layout); records: an array of abi.DISK_DT or of abi.CYLINDER_DT; host only"""
+    records = np.ascontiguousarray(records)
+    n = len(records)
+    x = np.zeros((n, 64), np.float32)
+    x[:, :40] = records.view(np.float32).reshape(n, 40)
+    xu = x.view(np.uint32)
+    xu[:, 40] = abi.MESH_DISK if records.dtype == abi.DISK_DT else abi.MESH_CYLINDER
+    xu[:, 42] = np.asarray(two_sided, bool).astype(np.uint32)
     x[:, 43:46], x[:, 46:49], x[:, 49:52], x[:, 52:54], x[:, 54:57] = ref_p, ref_p_error, ref_n, u, wi
     return x
 

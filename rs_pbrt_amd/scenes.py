@@ -760,7 +760,8 @@ class SceneBuilder:
 
     def add_disk(self, height=0.0, radius=1.0, innerradius=0.0, phimax=360.0, object_to_world=None, material=None, emit=None, two_sided=False, medium=(None, None)):
         """Shape "disk" (api.rs make_shapes, shapes/disk.rs:50-72) under the CTM object_to_world: Disk::new's radians(clamp(phimax, 0, 360)) in f32.
-        Served as a surface wherever spheres are (add_sphere); an emissive disk (emit) is accepted by rspt_scene_create and refused by rspt_render."""
+        Served as a surface wherever spheres are (add_sphere); an emissive disk (emit) is accepted by rspt_scene_create and refused by rspt_render
+        (unless the quadric-light gate is on: lib.set_quadric_lights)."""
         assert self.cur_object < 0, "disks inside ObjectBegin / ObjectEnd are not modelled (disks next to object instances are refused)"
         if material is None:
             material = abi.NO_MATERIAL

@@ -111,6 +111,9 @@ extern "C" {
     pub fn rspt_get_shade_math() -> u32;
     pub fn rspt_set_sphere_lights(on: u32) -> c_int;                               // the sphere-light gate (additive to ABI 27): process-wide, host only, off by default; RSPT_SPHERE_LIGHTS=0|1 overrides it
     pub fn rspt_get_sphere_lights() -> c_int;
+    pub fn rspt_set_quadric_lights(on: u32) -> c_int;                              // the quadric-light gate (additive to ABI 27): disk and cylinder area lights; process-wide, host only, off by default; RSPT_QUADRIC_LIGHTS=0|1 overrides it
+    pub fn rspt_get_quadric_lights() -> c_int;
+    pub fn rspt_quadric_light(x: *const f32, n: u64, out: *mut f32) -> c_int;      // stage hook: Disk / Cylinder area, sample, sample_with_ref_point, pdf_with_ref_point, DiffuseAreaLight::power; 64 floats per element
     pub fn rspt_sphere_light(x: *const f32, n: u64, out: *mut f32) -> c_int;       // stage hook: Sphere::area / sample / sample_with_ref_point / pdf_with_ref_point, 64 floats per element
     pub fn rspt_init(device: i32) -> c_int;
     pub fn rspt_shutdown();
